@@ -33,7 +33,9 @@ Other BASELINE configs (same metric/JSON contract, ``--config``):
 Usage: ``python bench.py --gpus N --steps K --warmup W``.  With N > 1 and no
 launcher the script starts its own ``torch.distributed.run`` group of N ranks
 (one per GPU, RCCL); under a launcher it checks WORLD_SIZE == N.  Rank 0 prints
-ONE JSON line.
+ONE JSON line.  ``--dump-outputs DIR`` also writes the last timed tick's results
+as ``DIR/<name>.npy``; ``--full`` adds whatever a config measures besides its
+timed ticks (a plain run does only what the result line needs).
 """
 
 from __future__ import annotations
@@ -73,6 +75,16 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=None, help="timed ticks (default 20; node: 8)")
     p.add_argument("--warmup", type=int, default=None, help="untimed ticks (default 5; node: 1)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed ticks, write what the last timed tick returned (the node health table and "
+                        "the scorer's per-series outputs) as DIR/<name>.npy, float32 / float64, at most 64 MB in "
+                        "all (a fixed seeded sample of the rows of a larger array); the inputs are seeded, so two "
+                        "builds run with the same arguments can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements that take runs of their own besides the timed ticks; a plain "
+                        "run only sets up, warms up, times the ticks and prints the result line (no config has "
+                        "such extra runs today: the CPU comparator and the other sizes / precisions are separate "
+                        "--config runs)")
     p.add_argument("--series", type=int, default=100_000)
     p.add_argument("--ring", type=int, default=10080)
     p.add_argument("--season", type=int, default=1440)
@@ -1028,6 +1040,38 @@ def run_cpu_baseline(args) -> None:
     }), flush=True)
 
 
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: all files of one run together (the option promises at most 64 MB)
+# what a tick hands its caller, by config: the Holt-Winters canary scorer's fit, band and verdict,
+# the LSTM scorers' reconstruction error; workspaces the kernels keep in the same dict are not outputs
+DUMP_KEYS = ("verdict", "count", "score", "sigma", "level", "trend", "best", "forecast", "upper", "lower",
+             "err", "zscore")
+
+
+def dump_outputs(path: str, out, health: torch.Tensor, world: int, rank: int) -> list:
+    """Write the last timed tick's results as ``<path>/<name>.npy`` (``<name>.rank<r>.npy``
+    for the shards of ranks > 0): the node health table and every ``DUMP_KEYS`` tensor of
+    the dict the tick returned.  Arrays are float32 (float64 for 64-bit values); one whose
+    share of ``DUMP_MAX_BYTES`` is too small for all its rows keeps a sorted sample of them
+    drawn with a fixed seed, the same rows in every run of the same shape."""
+    arrays = {"health": health}
+    if isinstance(out, dict):
+        arrays.update((k, out[k]) for k in DUMP_KEYS if isinstance(out.get(k), torch.Tensor))
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // (max(1, world) * len(arrays))
+    names = []
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        a = t.to(torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32).numpy()
+        a = a.reshape(-1) if a.ndim == 0 else a
+        rows = int(share // max(1, a[0].nbytes)) if a.shape[0] else 0
+        if a.shape[0] > max(1, rows):
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, rows), replace=False))]
+        fn = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(os.path.join(path, fn), np.ascontiguousarray(a))
+        names.append(fn)
+    return names
+
+
 def main():
     args = parse()
     if args.config == "cpu_baseline":
@@ -1076,12 +1120,14 @@ def main():
         dist.all_gather_object(parts, truth[0])
         truth = (sorted(set().union(*parts)), truth[1])
     pending = None  # pipelined ticks: (event, health copy, start time) of the tick in flight
+    last_out = None  # what the last tick returned (--dump-outputs)
 
     def run(k):
         """One tick; returns the detect latency of the tick that completed (or None)."""
-        nonlocal pending, health_host
+        nonlocal pending, health_host, last_out
         ts = time.perf_counter()
         r = tick(k)
+        last_out = r
         if not isinstance(r, InFlight):
             return time.perf_counter() - LAT_START.pop(k, ts)
         done, pending = pending, (r.event, r.host, LAT_START.pop(k, ts))
@@ -1123,6 +1169,9 @@ def main():
         torch.cuda.synchronize()
     barrier(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, table(health_host) if table is not None else health_host,
+                     world, rank)
     if graph_used is not None:
         meta["hip_graph"] = bool(graph_used())
     if deferred is not None:
