@@ -7,7 +7,7 @@ different distribution pattern, the threshold is lowered".
 
 Batched over series: ``baseline [N, nb]``, ``current [N, nc]`` with NaN
 padding.  Semantics match scipy's asymptotic forms (the oracle in
-``tests/test_pairwise.py``):
+``tests/test_models_reference.py``):
 
 * ``mannwhitneyu(b, c, alternative='two-sided', use_continuity=True,
   method='asymptotic')`` — tie-corrected normal approximation;
@@ -111,7 +111,9 @@ def friedman_pods(baseline: torch.Tensor, current: torch.Tensor, pods_b: int = 1
     tie = (tie.to(dt).reshape(N, nbk) * ok).sum(1)
     nblk = ok.sum(1).to(dt)
     Rj = r.sum(1)
-    chi = 12.0 / (nblk * k * (k + 1)).clamp(min=1e-30) * (Rj * Rj).sum(1) - 3 * nblk * (k + 1)
+    # 12 / (n k (k + 1)) sum R_j^2 - 3 n (k + 1) without its cancellation (sum R_j = n k (k + 1) / 2)
+    dev = Rj - (nblk * (k + 1) / 2)[:, None]
+    chi = 12.0 / (nblk * k * (k + 1)).clamp(min=1e-30) * (dev * dev).sum(1)
     cc = 1 - tie / (nblk * k * (k * k - 1)).clamp(min=1e-30)
     chi = chi / cc.clamp(min=1e-30)
     p = torch.special.gammaincc(torch.full_like(chi, (k - 1) / 2.0), (chi / 2).clamp(min=0))
@@ -192,7 +194,8 @@ def friedman(groups: torch.Tensor) -> torch.Tensor:
     r = r.reshape(N, nblk, k)
     tie = tie.reshape(N, nblk).sum(1)
     Rj = r.sum(1)  # [N, k]
-    chi = 12.0 / (nblk * k * (k + 1)) * (Rj * Rj).sum(1) - 3 * nblk * (k + 1)
+    dev = Rj - nblk * (k + 1) / 2
+    chi = 12.0 / (nblk * k * (k + 1)) * (dev * dev).sum(1)
     c = 1 - tie / (nblk * k * (k * k - 1))
     chi = chi / c.clamp(min=1e-30)
     p = torch.special.gammaincc(torch.tensor((k - 1) / 2.0, device=g.device), (chi / 2).clamp(min=0))

@@ -14,6 +14,28 @@
 
 extern __shared__ __attribute__((aligned(16))) char fm_biv_smem[];
 
+// Three block sums in one barrier round (red: 3 floats per wave); each is summed in blk_sum's order.
+__device__ __forceinline__ void blk_sum3(float& a, float& b, float& c, float* red) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  c = wave_sum(c);
+  const int nw = (int)(blockDim.x / FM_WAVE);
+  __syncthreads();
+  if (lane_id() == 0) {
+    red[3 * wave_id()] = a;
+    red[3 * wave_id() + 1] = b;
+    red[3 * wave_id() + 2] = c;
+  }
+  __syncthreads();
+  a = 0.f; b = 0.f; c = 0.f;
+  for (int i = 0; i < nw; ++i) {
+    a += red[3 * i];
+    b += red[3 * i + 1];
+    c += red[3 * i + 2];
+  }
+  __syncthreads();
+}
+
 template <typename TIN>
 __global__ __launch_bounds__(256) void bivariate_kernel(const BivArgs a) {
   const int n = blockIdx.x, tid = threadIdx.x;
@@ -35,18 +57,27 @@ __global__ __launch_bounds__(256) void bivariate_kernel(const BivArgs a) {
     }
   }
   // per-thread centred moments
-  const float mx_t = c > 0.f ? sx + ax / c : 0.f;
-  const float my_t = c > 0.f ? sy + ay / c : 0.f;
   const float cxx_t = c > 0.f ? axx - ax * ax / c : 0.f;
   const float cxy_t = c > 0.f ? axy - ax * ay / c : 0.f;
   const float cyy_t = c > 0.f ? ayy - ay * ay / c : 0.f;
-  const float N = blk_sum(c, red);
-  const float mx = N > 0.f ? blk_sum(c * mx_t, red) / N : 0.f;
-  const float my = N > 0.f ? blk_sum(c * my_t, red) / N : 0.f;
-  const float dmx = mx_t - mx, dmy = my_t - my;
-  const float Sxx = blk_sum(cxx_t + c * dmx * dmx, red);
-  const float Sxy = blk_sum(cxy_t + c * dmx * dmy, red);
-  const float Syy = blk_sum(cyy_t + c * dmy * dmy, red);
+  // Merge the thread means relative to a block-common centre (a first estimate of the mean),
+  // never as absolute values: a thread mean sx + ax / c rounds at ulp(level), which at level
+  // 1e4 with sigma 1 put ~1e-4 of the variance into the between-thread term and more than one
+  // ulp into the mean.  The offsets u_t are of the size of sigma, so everything below is.
+  float N = c, mx0 = c > 0.f ? c * (sx + ax / c) : 0.f, my0 = c > 0.f ? c * (sy + ay / c) : 0.f;
+  blk_sum3(N, mx0, my0, red);
+  mx0 = N > 0.f ? mx0 / N : 0.f;
+  my0 = N > 0.f ? my0 / N : 0.f;
+  const float ux_t = c > 0.f ? (sx - mx0) + ax / c : 0.f;
+  const float uy_t = c > 0.f ? (sy - my0) + ay / c : 0.f;
+  float ux = c * ux_t, uy = c * uy_t, unused = 0.f;
+  blk_sum3(ux, uy, unused, red);
+  ux = N > 0.f ? ux / N : 0.f;
+  uy = N > 0.f ? uy / N : 0.f;
+  const float mx = mx0 + ux, my = my0 + uy;
+  const float dmx = ux_t - ux, dmy = uy_t - uy;
+  float Sxx = cxx_t + c * dmx * dmx, Sxy = cxy_t + c * dmx * dmy, Syy = cyy_t + c * dmy * dmy;
+  blk_sum3(Sxx, Sxy, Syy, red);
   const float inv = 1.f / fmaxf(N, 1.f);
   const float vxx = Sxx * inv + a.eps, vxy = Sxy * inv, vyy = Syy * inv + a.eps;
   float det = vxx * vyy - vxy * vxy;

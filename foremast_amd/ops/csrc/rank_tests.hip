@@ -4,7 +4,8 @@
 //
 // Semantics: foremast_amd/models/pairwise.py (scipy asymptotic forms).
 // One 64-lane wave per series; four series per 256-thread workgroup.  The
-// pooled sample (n <= 1024) is staged in the wave's LDS slice and ranked by
+// pooled sample (fm_rank_lds_bytes within 64 KiB: round4(nb + nc) + round4(min(nb, nc))
+// <= 4032 floats per wave, e.g. 1344 + 1344) is staged in the wave's LDS slice and ranked by
 // exact pairwise counting: rank_i = #(x_j < x_i) + (#(x_j == x_i) + 1) / 2,
 // which gives average ranks under ties and the tie term sum(t^3 - t) =
 // sum_i (eq_i^2 - 1) in the same sweep.  All lanes read the same x_j per
@@ -122,15 +123,19 @@ __device__ __forceinline__ void friedman_wave(const RankArgs& a, const float* x,
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  const float r = lane < k ? R[lane] : 0.f;
-  const float ssq = wave_sum(r * r);
   const float nb = wave_sum(cnt);
+  const float fk = (float)k;
+  // The rank sums add up to n k (k + 1) / 2, so 12 / (n k (k + 1)) sum R_j^2 - 3 n (k + 1) equals
+  // 12 / (n k (k + 1)) sum (R_j - n (k + 1) / 2)^2.  The textbook form subtracts two terms of
+  // ~3 n (k + 1); in fp32 their rounding leaves chi ~1e-5 where it is 0, and with one dof
+  // (p ~ 1 - 0.8 sqrt(chi)) that is ~3e-3 of p.  The deviations are half-integers: exact.
+  const float dr = lane < k ? R[lane] - 0.5f * nb * (fk + 1.f) : 0.f;
+  const float ssq = wave_sum(dr * dr);
   tie = wave_sum(tie);
   nblk_out = nb;
   p_out = 1.f;
   if (nb > 0.f && k >= 2) {
-    const float fk = (float)k;
-    const float chi = 12.f / (nb * fk * (fk + 1.f)) * ssq - 3.f * nb * (fk + 1.f);
+    const float chi = 12.f / (nb * fk * (fk + 1.f)) * ssq;
     const float c = 1.f - tie / (nb * fk * (fk * fk - 1.f));
     if (c > 0.f) p_out = chi2_sf(fmaxf(chi / c, 0.f), k - 1);
   }

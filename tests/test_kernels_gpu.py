@@ -230,6 +230,12 @@ def test_window_stats_short_window_odd_head_and_offset(K, dtype):
     np.testing.assert_allclose(out["score"].cpu().numpy(), d.score.numpy(), rtol=1e-4)
 
 
+def _near_alpha(p, alpha):
+    """Reference p-values within the kernel's p tolerance (rtol 2e-3, atol 1e-5) of alpha: the
+    only rows on which a decision may differ from the fp64 reference (at most 2 % of a case)."""
+    return (p - alpha).abs() <= 2e-3 * alpha + 1e-5
+
+
 def test_rank_tests_kernel(K):
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(3)
@@ -248,8 +254,12 @@ def test_rank_tests_kernel(K):
     np.testing.assert_allclose(p[:, 1].numpy(), ref.p_wilcoxon.numpy(), rtol=2e-3, atol=1e-5)
     np.testing.assert_allclose(p[:, 2].numpy(), ref.p_kruskal.numpy(), rtol=2e-3, atol=1e-5)
     dref = pw_ref.pairwise_differs(ref, pw_ref.PW_ALL, 0.05)
-    agree = (out["differs"].cpu().bool() == dref).float().mean()
-    assert agree > 0.99
+    n_small = torch.minimum(ref.n_base, ref.n_cur)
+    near = ((n_small >= 20) & _near_alpha(ref.p_mw, 0.05)) | ((ref.n_pairs >= 20) & _near_alpha(ref.p_wilcoxon, 0.05)) \
+        | ((n_small >= 5) & _near_alpha(ref.p_kruskal, 0.05))
+    assert int(near.sum()) <= 0.02 * N
+    assert torch.equal(out["differs"].cpu().bool()[~near], dref[~near])
+    assert 0 < int(dref.sum()) < N
     # the baseline window means (the mean-shift rule's centre)
     np.testing.assert_allclose(out["base_mean"].cpu().numpy(), np.nanmean(b, 1), rtol=1e-5, atol=1e-6)
 
@@ -321,7 +331,9 @@ def test_rank_tests_kernel_friedman(K):
     np.testing.assert_array_equal(fr[:, 1].numpy(), ref.n_blocks.numpy())
     np.testing.assert_allclose(fr[:, 0].numpy(), ref.p_friedman.numpy(), rtol=2e-3, atol=1e-5)
     dref = pw_ref.pairwise_differs(ref, pw_ref.PW_FRIEDMAN, 0.05, min_friedman=5)
-    assert (out["differs"].cpu().bool() == dref).float().mean() > 0.99
+    near = (ref.n_blocks >= 5) & _near_alpha(ref.p_friedman, 0.05)
+    assert int(near.sum()) <= 0.02 * N
+    assert torch.equal(out["differs"].cpu().bool()[~near], dref[~near])
     assert 0 < int(dref.sum()) < N
     # the other tests are unchanged when Friedman rides along
     out2 = K.rank_tests(tb, tc, pw_ref.PW_ALL, 0.05, pods=(P, P), want_friedman=True)

@@ -182,6 +182,58 @@ def test_bivariate():
     assert d2[0, 0].item() < 0.1
 
 
+def _np_bivariate_fit(h):
+    """Independent fp64 fit (numpy): mean and biased covariance over jointly valid points."""
+    mean, cov, cnt = [], [], []
+    for row in np.asarray(h, dtype=np.float64):
+        v = row[~np.isnan(row).any(1)]
+        if len(v) == 0:
+            mean.append([0.0, 0.0]), cov.append([0.0, 0.0, 0.0]), cnt.append(0)
+            continue
+        m = v.mean(0)
+        d = v - m
+        mean.append(m)
+        cov.append([(d[:, 0] ** 2).mean(), (d[:, 0] * d[:, 1]).mean(), (d[:, 1] ** 2).mean()])
+        cnt.append(len(v))
+    return np.array(mean), np.array(cov), np.array(cnt)
+
+
+@pytest.mark.parametrize("level", [1e4, 1e6])
+def test_bivariate_fit_keeps_the_mean_at_a_large_level(level):
+    """fp32 windows at a large level, sigma 1: the fit (also the product's CPU path) must match
+    an fp64 fit of the same fp32 values, the mean to one fp32 ulp of the level and the
+    covariance to 1e-5.  An fp32 accumulation of the 700 points stays within that at 1e4 only
+    because the host sum is pairwise; at 1e6 it loses the mean by ~0.1 sigma and the covariance
+    by 6e-3.  fp64 windows give an fp64 fit."""
+    rng = np.random.default_rng(21)
+    N, T = 8, 700
+    h = rng.multivariate_normal([0, 0], [[1.0, 0.5], [0.5, 1.0]], size=(N, T)) + [level, -level]
+    h = h.astype(np.float32)
+    h[2, 5:40, 0] = np.nan
+    h[3, ::3, 1] = np.nan
+    mean, cov, cnt = _np_bivariate_fit(h)
+    fit = bivariate.fit_bivariate(torch.tensor(h))
+    assert fit.mean.dtype == torch.float32 and fit.cov.dtype == torch.float32
+    np.testing.assert_array_equal(fit.count.numpy(), cnt)
+    ulp = np.spacing(np.float32(level))
+    assert np.abs(fit.mean.double().numpy() - mean).max() <= ulp
+    np.testing.assert_allclose(fit.cov.double().numpy(), cov, rtol=1e-5)
+    # fp64 in, fp64 out (the oracle of the GPU tests), and d2 follows the fit's type
+    fit64 = bivariate.fit_bivariate(torch.tensor(h, dtype=torch.float64))
+    assert fit64.mean.dtype == torch.float64 and fit64.cov.dtype == torch.float64
+    np.testing.assert_allclose(fit64.mean.numpy(), mean, rtol=1e-14)
+    np.testing.assert_allclose(fit64.cov.numpy(), cov, rtol=1e-10)
+    x = torch.tensor(mean[:, None, :] + [[1.5, -0.5], [0.0, 3.0]])
+    d2 = bivariate.mahalanobis2(fit64, x, eps=0.0)
+    assert d2.dtype == torch.float64
+    want = []
+    for n in range(N):
+        S = np.array([[cov[n, 0], cov[n, 1]], [cov[n, 1], cov[n, 2]]])
+        want.append([dv @ np.linalg.inv(S) @ dv for dv in (x[n].numpy() - mean[n])])
+    np.testing.assert_allclose(d2.numpy(), np.array(want), rtol=1e-9)
+    assert bivariate.mahalanobis2(fit, x.float()).dtype == torch.float32
+
+
 def test_prophet_lite_recovers_trend_and_seasonality():
     """Parity unpinned (the prophet package is not installed): checks the
     batched ridge fit against the generating model, gap handling, and that a
