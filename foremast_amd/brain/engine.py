@@ -526,6 +526,8 @@ class StreamingShard:
             self.out = K.window_stats(h.data, head, length, spec, out=self.out)
         elif self.algorithm == "seasonal_decompose":
             self.out = K.decompose_score(h.data, h.head, h.length, self.spec.season, spec, out=self.out)
+        elif self.algorithm == "prophet":
+            self.out = K.prophet_score(h.data, h.head, h.length, self.spec.season, spec, out=self.out)
         else:
             raise ValueError(f"algorithm {self.algorithm!r} is not a streaming univariate scorer")
         return self.out
@@ -562,6 +564,12 @@ class StreamingShard:
             f = dec_ref.forecast_decomposition(fc, h)
             sigma, n_valid = fc.sigma, fc.n_valid
             extra = {"level": fc.level, "slope": fc.slope, "sigma": fc.sigma}
+        elif self.algorithm == "prophet":
+            from ..models import prophet_lite as pl_ref
+            fit = pl_ref.fit_prophet_window(y, self.spec.season)
+            f = pl_ref.forecast_window(fit, h)
+            sigma, n_valid = fit.sigma, fit.n_valid
+            extra = {"sigma": fit.sigma}
         elif self.mode is not None:
             fit = sm_ref.fit_smoothing(y, self.mode, self.grid.cpu(), m=self.spec.season)
             f = sm_ref.forecast(fit, h)

@@ -196,11 +196,14 @@ class StreamingMonitor:
         season = max(2, int(round(86400.0 / self.step)))
         algo = self.cfg.algorithm if self.cfg.algorithm in ("holt_winters", "exponential_smoothing",
                                                             "double_exponential_smoothing", "moving_average",
-                                                            "moving_average_all", "seasonal_decompose") \
+                                                            "moving_average_all", "seasonal_decompose",
+                                                            "prophet") \
             else "moving_average_all"
         if algo == "holt_winters" and self.R < 2 * season:
             algo = "double_exponential_smoothing"
         if algo == "seasonal_decompose" and self.R < 2 * season + 1:
+            algo = "moving_average_all"
+        if algo == "prophet" and self.R < 2:
             algo = "moving_average_all"
         dev = self.device
         spec = ShardSpec(n_series=capacity, ring_len=self.R, season=season, pods=1, window=self.W, algorithm=algo,

@@ -106,3 +106,101 @@ def forecast(fit: ProphetFit, ts: torch.Tensor) -> torch.Tensor:
     """``ts [B, C]`` absolute timestamps → forecast ``[B, C]``."""
     X = _features(ts.to(torch.float64), fit.t0, fit.span, fit.cps, fit.seasons)
     return ((X @ fit.beta[:, :, None])[:, :, 0] * fit.yscale[:, None]).to(torch.float32)
+
+
+# ---------------------------------------------------------------------------------
+# Window-scaled variant (streaming shards, ops/csrc/prophet.hip)
+# ---------------------------------------------------------------------------------
+#
+# Every series of a ring shares the step and the window, so with time scaled by the
+# WINDOW (logical index t = 0 .. T-1, s = t / (T-1)) instead of by each series' first and
+# last valid sample, the design matrix X [T, P] is the same for all of them: the fit is
+# rhs = X' (w y) per series against one shared table.  The seasons are decided by the
+# window as well (daily iff T-1 >= 2m, weekly iff T-1 >= 14m, m = samples per day).  The
+# Fourier phase origin is the window's first sample: the ridge is isotropic on each
+# (sin k, cos k) pair, so the origin changes neither forecasts nor residuals.
+
+@dataclass
+class ProphetWindowFit(ProphetFit):
+    T: int = 0
+    m: int = 0
+    n_changepoints: int = 10
+    cp_range: float = 0.8
+    phase: float = 0.0
+
+
+def window_seasons(T: int, m: int) -> Tuple[Tuple[float, int], ...]:
+    """``((period in samples, order), ...)`` of a window of ``T`` samples, ``m`` per day."""
+    seasons: List[Tuple[float, int]] = []
+    if T - 1 >= 2 * m:
+        seasons.append((float(m), 4))
+    if T - 1 >= 14 * m:
+        seasons.append((float(7 * m), 3))
+    return tuple(seasons)
+
+
+def _window_features(t: torch.Tensor, T: int, m: int, n_changepoints: int, cp_range: float,
+                     phase: float = 0.0) -> torch.Tensor:
+    """Logical sample indices ``t [...]`` (fp64) → features ``[..., P]``; ``phase``
+    shifts the Fourier origin (in samples)."""
+    s = t / float(T - 1)
+    cps = torch.arange(1, n_changepoints + 1, dtype=t.dtype, device=t.device) / (n_changepoints + 1) * cp_range
+    parts = [torch.stack([torch.ones_like(s), s], -1), torch.clamp(s[..., None] - cps, min=0.0)]
+    for period, order in window_seasons(T, m):
+        k = torch.arange(1, order + 1, dtype=t.dtype, device=t.device)
+        ang = 2 * math.pi * ((t[..., None] + phase) / period) * k
+        parts += [torch.sin(ang), torch.cos(ang)]
+    return torch.cat(parts, -1)
+
+
+def design_window(T: int, m: int, hmax: int, n_changepoints: int = 10, cp_range: float = 0.8,
+                  ridge_cp: float = 10.0, ridge: float = 1e-4, phase: float = 0.0):
+    """Shared tables of a ``T``-sample window (fp64): ``X [T, P]``, the horizon rows
+    ``XH [hmax, P]`` (features of logical index ``T-1+h``, h = 1..hmax), the ridge vector
+    ``reg [P]`` and the gap-free normal matrix ``A_dense = X'X + diag(reg)``."""
+    if T < 2 or m < 2:
+        raise ValueError("design_window needs T >= 2 and m >= 2")
+    dt = torch.float64
+    X = _window_features(torch.arange(T, dtype=dt), T, m, n_changepoints, cp_range, phase)
+    XH = _window_features(torch.arange(T, T + hmax, dtype=dt), T, m, n_changepoints, cp_range, phase)
+    P = X.shape[1]
+    reg = torch.full((P,), ridge, dtype=dt)
+    reg[2:2 + n_changepoints] = ridge_cp
+    return X, XH, reg, X.T @ X + torch.diag(reg)
+
+
+def fit_prophet_window(hist: torch.Tensor, m: int, n_changepoints: int = 10, cp_range: float = 0.8,
+                       ridge_cp: float = 10.0, ridge: float = 1e-4, phase: float = 0.0) -> ProphetWindowFit:
+    """Window-scaled fit of ``hist [N, T]`` (NaN = missing) in fp64, in data units
+    (``beta`` is :func:`fit_prophet`'s ``beta * yscale``; the fit is linear in y)."""
+    N, T = hist.shape
+    dev, dt = hist.device, torch.float64
+    X, _, reg, _ = design_window(T, m, 1, n_changepoints, cp_range, ridge_cp, ridge, phase)
+    X, reg = X.to(dev), reg.to(dev)
+    P = X.shape[1]
+    y = hist.to(dt)
+    w = (~torch.isnan(y)).to(dt)
+    y = torch.nan_to_num(y, nan=0.0)
+    XX = (X[:, :, None] * X[:, None, :]).reshape(T, P * P)
+    A = (w @ XX).reshape(N, P, P) + torch.diag(reg)[None]
+    rhs = y @ X  # y is 0 where missing
+    beta = torch.linalg.solve(A, rhs[:, :, None])[:, :, 0]
+    r = (y - beta @ X.T) * w
+    n = w.sum(1)
+    sigma = torch.sqrt((r * r).sum(1) / (n - P).clamp(min=1.0))
+    cps = (torch.arange(1, n_changepoints + 1, dtype=dt, device=dev) / (n_changepoints + 1) * cp_range)
+    return ProphetWindowFit(beta=beta, sigma=sigma.to(torch.float32), n_valid=n.to(torch.int32),
+                            t0=torch.zeros(N, dtype=dt, device=dev),
+                            span=torch.full((N,), float(T - 1), dtype=dt, device=dev),
+                            cps=cps[None, :].expand(N, -1).contiguous(),
+                            yscale=torch.ones(N, dtype=dt, device=dev), seasons=window_seasons(T, m),
+                            T=T, m=m, n_changepoints=n_changepoints, cp_range=cp_range, phase=phase)
+
+
+def forecast_window(fit: ProphetWindowFit, horizons: torch.Tensor) -> torch.Tensor:
+    """``horizons [C]`` or ``[N, C]`` (steps past the window's last sample, >= 1) → ``[N, C]``."""
+    h = horizons.to(fit.beta.device, torch.float64)
+    XH = _window_features(float(fit.T - 1) + h, fit.T, fit.m, fit.n_changepoints, fit.cp_range, fit.phase)
+    if h.dim() == 1:
+        return (fit.beta @ XH.T).to(torch.float32)
+    return (XH * fit.beta[:, None, :]).sum(-1).to(torch.float32)

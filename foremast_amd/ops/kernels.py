@@ -1082,6 +1082,125 @@ def decompose_score(hist: torch.Tensor, head: int, length: int, m: int, det: Det
 
 
 # ---------------------------------------------------------------------------------
+# Window-scaled Prophet scorer (prophet.hip)
+# ---------------------------------------------------------------------------------
+
+class ProphetArgs(C.Structure):
+    _fields_ = [("hist", C.c_void_p), ("ld", C.c_longlong), ("ring_len", C.c_int), ("head", C.c_int),
+                ("T", C.c_int), ("N", C.c_int), ("bf16", C.c_int), ("P", C.c_int), ("PP", C.c_int),
+                ("hmax", C.c_int), ("X", C.c_void_p), ("XH", C.c_void_p), ("A", C.c_void_p), ("L", C.c_void_p),
+                ("LT", C.c_void_p), ("reg", C.c_void_p), ("XXp", C.c_void_p), ("beta", C.c_void_p),
+                ("sigma", C.c_void_p), ("nvalid", C.c_void_p), ("mask", C.c_void_p), ("defer", C.c_void_p),
+                ("S", C.c_int), ("_pad", C.c_int), ("det", nat.DetectArgs)]
+
+
+nat.register("fm_prophet_score", [C.POINTER(ProphetArgs), C.c_void_p])
+nat.register("fm_prophet_args_size", [], C.c_longlong)
+
+PROPHET_PAD = (12, 20, 26, 32)   # table widths the kernels are compiled for (P is padded up)
+PROPHET_HMAX = 64                # horizon rows of the forecast table
+_PROPHET_TABLES: Dict[tuple, Dict[str, object]] = {}
+
+
+def prophet_tables(T: int, m: int, device, n_changepoints: int = 10, cp_range: float = 0.8,
+                   ridge_cp: float = 10.0, ridge: float = 1e-4) -> Dict[str, object]:
+    """Device tables of a ``T``-sample window (models/prophet_lite.py ``design_window``,
+    fp64 on the host, cast to fp32), cached per geometry and device: ``X [T, PP]``,
+    ``XH [64, PP]``, ``A [PP, PP]``, its Cholesky factor ``L`` (diagonal stored as
+    ``1 / L[k][k]``) and ``LT``, ``reg [PP]``, and ``XXp [T+1, PP(PP+1)/2]``, the prefix sums of
+    the lower triangle of ``x_t x_t'``.  Columns ``P .. PP-1`` are padding (zero
+    features, unit diagonal: their coefficients are exactly 0)."""
+    device = torch.device(device)
+    key = (int(T), int(m), int(n_changepoints), float(cp_range), float(ridge_cp), float(ridge),
+           device.type, device.index if device.index is not None or device.type != "cuda"
+           else torch.cuda.current_device())
+    tab = _PROPHET_TABLES.get(key)
+    if tab is not None:
+        return tab
+    from ..models import prophet_lite as pl
+    X, XH, reg, A = pl.design_window(int(T), int(m), PROPHET_HMAX, n_changepoints, cp_range, ridge_cp, ridge)
+    P = X.shape[1]
+    _need(P <= PROPHET_PAD[-1], f"prophet model has {P} terms, the kernel takes at most {PROPHET_PAD[-1]}")
+    PP = next(p for p in PROPHET_PAD if p >= P)
+    dt = torch.float64
+
+    def pad(t, rows):
+        o = torch.zeros((rows, PP), dtype=dt)
+        o[:t.shape[0], :P] = t
+        return o
+    Ap = torch.eye(PP, dtype=dt)
+    Ap[:P, :P] = A
+    regp = torch.ones(PP, dtype=dt)
+    regp[:P] = reg
+    L = torch.linalg.cholesky(Ap)
+    d = torch.diagonal(L).clone()
+    L = L - torch.diag(d) + torch.diag(1.0 / d)
+    # prefix sums over t of the lower triangle of x_t x_t' (a run of missing samples is two rows)
+    Xp = pad(X, int(T))
+    ii, jj = torch.tril_indices(PP, PP)
+    XXp = torch.cat([torch.zeros((1, ii.numel()), dtype=dt), torch.cumsum(Xp[:, ii] * Xp[:, jj], 0)])
+    f32 = dict(dtype=torch.float32, device=device)
+    tab = {"P": P, "PP": PP, "X": Xp.to(**f32), "XXp": XXp.to(**f32), "XH": pad(XH, PROPHET_HMAX).to(**f32),
+           "A": Ap.to(**f32), "L": L.contiguous().to(**f32), "LT": L.T.contiguous().to(**f32),
+           "reg": regp.to(**f32)}
+    _PROPHET_TABLES[key] = tab
+    return tab
+
+
+def prophet_score(hist: torch.Tensor, head: int, length: int, m: int, det: DetectSpec,
+                  out: Optional[Dict[str, torch.Tensor]] = None, n_changepoints: int = 10,
+                  cp_range: float = 0.8, ridge_cp: float = 10.0, ridge: float = 1e-4,
+                  want_beta: bool = False) -> Dict[str, torch.Tensor]:
+    """Window-scaled Prophet scorer (``ML_ALGORITHM=prophet`` on streaming shards): ridge
+    fit of trend + changepoint hinges + daily / weekly Fourier terms over the ring's
+    logical window against tables shared by every series (models/prophet_lite.py
+    ``fit_prophet_window``; ``m`` samples per day), then the fused band / verdict
+    epilogue with sigma the residual standard deviation (no horizon factor).  Returns
+    ``sigma`` / ``nvalid`` ``[N]``, the detection outputs, and ``beta [N, P]`` (a view of
+    the workspace) with ``want_beta``."""
+    lib = nat.require()
+    _hist_check(hist, head, length)
+    _need(length >= 2, f"window of {length} samples: prophet needs at least 2")
+    _need(int(m) >= 2, f"period {m}: prophet needs m >= 2")
+    bf16 = hist.dtype == torch.bfloat16
+    _need(hist.stride(0) % (8 if bf16 else 4) == 0 and hist.data_ptr() % 16 == 0,
+          "hist rows must be 16-byte aligned for vector loads")
+    hmax = det.max_horizon
+    if hmax is None:
+        hmax = int(det.horizons.max()) if det.horizons.numel() else 1  # one sync: pass max_horizon per tick
+    _need(1 <= int(hmax) <= PROPHET_HMAX, f"horizons up to {hmax}: the prophet kernel takes 1..{PROPHET_HMAX}")
+    N, dev = hist.shape[0], hist.device
+    tab = prophet_tables(length, m, dev, n_changepoints, cp_range, ridge_cp, ridge)
+    P, PP = tab["P"], tab["PP"]
+    R = hist.shape[1]
+    Q = (R + 31) // 32
+    out = {} if out is None else out
+    f32 = dict(dtype=torch.float32, device=dev)
+    for k in ("sigma", "nvalid"):
+        if k not in out:
+            out[k] = torch.empty(N, **f32)
+    if "_beta" not in out or out["_beta"].shape != (N, PP):
+        out["_beta"] = torch.empty((N, PP), **f32)
+    if "_mask" not in out or out["_mask"].shape != (N, Q):
+        out["_mask"] = torch.empty((N, Q), dtype=torch.int32, device=dev)
+    if "_defer" not in out or out["_defer"].numel() != N + 1:
+        # [count, gapped series...]: the kernels leave the count zero between calls
+        out["_defer"] = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+    a = ProphetArgs()
+    a.hist, a.ld, a.ring_len, a.head, a.T, a.N = nat.ptr(hist), hist.stride(0), R, int(head), int(length), N
+    a.bf16, a.P, a.PP, a.hmax = int(bf16), P, PP, PROPHET_HMAX
+    a.X, a.XH, a.A, a.L, a.LT, a.reg, a.XXp = (nat.ptr(tab[k]) for k in ("X", "XH", "A", "L", "LT", "reg", "XXp"))
+    a.beta, a.sigma, a.nvalid = nat.ptr(out["_beta"]), nat.ptr(out["sigma"]), nat.ptr(out["nvalid"])
+    a.mask, a.defer = nat.ptr(out["_mask"]), nat.ptr(out["_defer"])
+    a.S = max(1, min(8, Q))
+    _fill_detect(a.det, det, N, dev, out)
+    nat.check(lib.fm_prophet_score(C.byref(a), nat.stream_handle(dev)), "fm_prophet_score")
+    if want_beta:
+        out["beta"] = out["_beta"][:, :P]
+    return out
+
+
+# ---------------------------------------------------------------------------------
 # K3 cached model: Holt-Winters state extraction + O(1) update/detect (hw_state.hip)
 # ---------------------------------------------------------------------------------
 
