@@ -11,6 +11,10 @@
   ``models/detect.py`` ``detect`` on the GPU, the only device path this model had) at
   B = 2048 x 10,080, alternated with ``prophet_score`` at the same B in the same process.
 
+* ``--admission``: ``prophet_fit_state`` (the resident rollout engine's admission fit: the
+  same launches without the detection epilogue, plus the forecast-state kernel) against
+  ``prophet_score`` on the same rows, alternated.
+
 Needs a GPU (exit status 2 without one).
 """
 
@@ -129,6 +133,41 @@ def _versus_torch(K, B: int, calls: int, warmup: int, rounds: int, dev) -> Dict:
     return res
 
 
+def _admission(K, N: int, calls: int, warmup: int, rounds: int, dev) -> List[Dict]:
+    """The rollout engine's admission fit (``prophet_fit_state``: fit + forecast state, no
+    detection) against ``prophet_score`` on the same rows, alternated in one process."""
+    rows = []
+    for kind in ("dense", "miss", "outage"):
+        ring = _ring(N, kind, dev)
+        cur = ring[:, T - C:].float().contiguous()
+        spec = _spec(K, N, dev, cur)
+        out_s: Dict[str, torch.Tensor] = {}
+        out_f: Dict[str, torch.Tensor] = {}
+
+        def score():
+            K.prophet_score(ring, 0, T, M, spec, out=out_s)
+
+        def fit_state():
+            K.prophet_fit_state(ring, 0, T, M, out=out_f)
+        for _ in range(warmup):
+            score()
+            fit_state()
+        torch.cuda.synchronize()
+        s_ms, f_ms = [], []
+        for _ in range(rounds):
+            s_ms.append(_timed(score, calls))
+            f_ms.append(_timed(fit_state, calls))
+        same = all(torch.equal(out_s[k].view(torch.int32), out_f[k].view(torch.int32))
+                   for k in ("_beta", "sigma", "nvalid"))
+        rows.append({"input": kind, "series": N, "T": T, "m": M, "rounds": rounds, "calls_per_round": calls,
+                     "prophet_score_ms": sorted(s_ms)[rounds // 2], "prophet_fit_state_ms": sorted(f_ms)[rounds // 2],
+                     "prophet_score_ms_all": s_ms, "prophet_fit_state_ms_all": f_ms, "same_bits": same})
+        print(json.dumps(rows[-1]), flush=True)
+        del ring, cur, spec, out_s, out_f
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("out", help="path of the JSON result")
@@ -139,6 +178,9 @@ def main(argv=None) -> int:
     p.add_argument("--rounds", type=int, default=5)
     p.add_argument("--skip-product", action="store_true")
     p.add_argument("--skip-torch", action="store_true")
+    p.add_argument("--admission", action="store_true",
+                   help="also time prophet_fit_state (the rollout engine's admission fit) against prophet_score "
+                        "on --series rows, alternated")
     args = p.parse_args(argv)
     if not torch.cuda.is_available():
         print("foremast_amd.benchmarks.prophet needs a GPU", file=sys.stderr)
@@ -154,6 +196,8 @@ def main(argv=None) -> int:
         res["outage_over_dense"] = next(r for r in rows if r["input"] == "outage")["ms_per_call"] / dense
     if not args.skip_torch:
         res["versus_torch"] = _versus_torch(K, args.batch, max(args.calls, 1), args.warmup, args.rounds, dev)
+    if args.admission:
+        res["admission"] = _admission(K, args.series, max(args.calls, 1), args.warmup, args.rounds, dev)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")

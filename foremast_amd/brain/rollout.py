@@ -16,7 +16,10 @@ state instead:
   fixed at creation, so refitting it every cycle would recompute the same
   model — and reduced to a forecast state per (job, metric) row: level,
   trend, the 16 forecast offsets of the current window's horizons, sigma,
-  fitted grid point (h-step variance) and valid points.  The baseline pods'
+  fitted grid point (h-step variance) and valid points (``ML_ALGORITHM=prophet``:
+  level, slope per sample and the 14 harmonic coefficients of the window-scaled
+  model, ``models/prophet_lite.py`` ``window_state``, evaluated at any horizon by
+  ``prophet_state_detect_kernel`` in place of the launch below).  The baseline pods'
   window ``[start - W, start]`` is fetched once, batched by pod family.  Rows,
   thresholds, pod slots and window maps are set with array operations over the
   admitted batch (no per-row Python objects);
@@ -76,6 +79,7 @@ from ..models import decompose as dec_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
 from ..models import pairwise as pw_ref
+from ..models import prophet_lite as pr_ref
 from ..models import smoothing as sm_ref
 from ..parallel.roster import ChangeLog
 from ..store.jobstore import JobStore
@@ -88,6 +92,7 @@ from .resident import Key, ResidentHistory, fetch_decode, quote_selector, range_
 log = logging.getLogger("foremast.rollout")
 
 HB = 16  # forecast offsets kept per row (kernels.HALF_HB): horizons 1..16 of the current window
+HARM = pr_ref.STATE_HARM  # harmonic coefficients kept per row with ML_ALGORITHM=prophet
 _NO_ROWS = np.zeros(0, dtype=np.int64)
 _NO_KEYS = np.zeros(0, dtype=np.uint64)
 
@@ -223,6 +228,9 @@ class RolloutMonitor:
         self.P = max(1, int(pods))
         self.season = max(2, int(round(86400.0 / self.step)))
         self.m_detect = max(self.season, HB)
+        # ML_ALGORITHM=prophet: rows keep the harmonic state of the window-scaled model
+        # (models/prophet_lite.py window_state) and are scored by its own kernel
+        self.prophet = self.cfg.algorithm == "prophet"
         self.decode_threads = max(1, int(decode_threads or native.default_threads()))
         self.apps_per_query = max(1, int(apps_per_query))
         self.claim_limit = claim_limit
@@ -358,6 +366,8 @@ class RolloutMonitor:
         st = {k: torch.zeros(cap, **f32) for k in ("level", "trend", "sigma", "nvalid")}
         st["best"] = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         st["season_hb"] = torch.zeros((cap, HB), **f32)
+        if self.prophet:  # the Fourier terms of the prophet state (season_hb stays zero, trend is the slope)
+            st["harm"] = torch.zeros((cap, HARM), **f32)
         if old is not None:
             for k, t in new.items():
                 t[:n].copy_(getattr(self, k))
@@ -725,6 +735,8 @@ class RolloutMonitor:
             t_fit = hist.t_last - dv * self.step
             data, head, length = hist.gather(hrows[sel].tolist(), dv)
             st = self._fit_state(data, head, length)
+            if self.prophet and "harm" not in st:  # a window too short for the model: no Fourier terms
+                st["harm"] = torch.zeros((len(sel), HARM), device=self.device)
             idx = torch.from_numpy(b.rows[sel]).to(self.device)
             for k, v in st.items():
                 self.state[k][idx] = v.to(self.state[k].dtype)
@@ -822,6 +834,8 @@ class RolloutMonitor:
             algo = "double_exponential_smoothing"
         if algo == "seasonal_decompose" and length < 2 * m + 1:
             algo = "moving_average_all"
+        if algo == "prophet" and length < 2:
+            algo = "moving_average_all"
         return algo
 
     def _fit_state(self, data: torch.Tensor, head: int, length: int) -> Dict[str, torch.Tensor]:
@@ -831,6 +845,8 @@ class RolloutMonitor:
         h-step variance)."""
         algo = self._algo_for(length)
         k, dev, cfg = data.shape[0], self.device, self.cfg
+        if algo == "prophet":
+            return self._fit_state_prophet(data, head, length)
         hs = torch.arange(1, HB + 1, dtype=torch.int32, device=dev)
         mode = sm_ref.MODE_BY_NAME.get(algo)
         if self.gpu:
@@ -888,6 +904,25 @@ class RolloutMonitor:
         ws = ma_ref.window_stats(y, cfg.ma_window if algo == "moving_average" else None)
         return {"level": ws.mean, "trend": torch.zeros(k), "sigma": ws.std, "nvalid": ws.count.float(),
                 "season_hb": torch.zeros((k, HB)), "best": torch.full((k,), -1, dtype=torch.int32)}
+
+    def _fit_state_prophet(self, data: torch.Tensor, head: int, length: int) -> Dict[str, torch.Tensor]:
+        """The window-scaled prophet model (models/prophet_lite.py ``fit_prophet_window``) of
+        each row, reduced to its harmonic state: ``trend`` holds the slope per sample and
+        ``harm`` the 14 Fourier coefficients at the window's last sample; ``season_hb`` is
+        zero and ``best`` -1 (sigma is the residual standard deviation at every horizon)."""
+        k, dev = data.shape[0], self.device
+        if self.gpu:
+            from ..ops import kernels as K
+            out = K.prophet_fit_state(data, head, length, self.season)
+            level, slope, harm, sigma, nvalid = (out[n] for n in ("level", "slope", "harm", "sigma", "nvalid"))
+        else:
+            idx = (torch.arange(length) + head) % data.shape[1]
+            fit = pr_ref.fit_prophet_window(data.index_select(1, idx).float(), self.season)
+            level, slope, harm = (t.float() for t in pr_ref.window_state(fit))
+            sigma, nvalid = fit.sigma, fit.n_valid.float()
+        return {"level": level, "trend": slope, "sigma": sigma, "nvalid": nvalid, "harm": harm,
+                "season_hb": torch.zeros((k, HB), device=dev),
+                "best": torch.full((k,), -1, dtype=torch.int32, device=dev)}
 
     def _fam_index(self, fkeys: np.ndarray, cols_of, s_of) -> np.ndarray:
         """Family index of each row (by the decoder's family key; names interned once)."""
@@ -1242,8 +1277,12 @@ class RolloutMonitor:
                             tick_min=self._tick_dev[1:2], last_ncol=Wc)
         st = dict(self.state)
         st.update(self.out)
-        out = K.hw_detect_deferred(st, spec, self.m_detect, self.m_detect,
-                                   grid=self.grid_all if cfg.horizon_variance else None)
+        if self.prophet:  # same epilogue, the forecast evaluated from the harmonic state
+            st["slope"] = st["trend"]
+            out = K.prophet_state_detect(st, self.season, spec, out=st)
+        else:
+            out = K.hw_detect_deferred(st, spec, self.m_detect, self.m_detect,
+                                       grid=self.grid_all if cfg.horizon_variance else None)
         self.out = {k: out[k] for k in ("forecast", "upper", "lower", "count", "verdict", "score")}
         self._rec_host.copy_(self._rec_dev, non_blocking=True)
 
@@ -1309,9 +1348,12 @@ class RolloutMonitor:
                                               cfg.min_wilcoxon, cfg.min_kruskal, cfg.min_friedman)
         s = self.state
         h = self.hz.long()
-        f = s["level"][:, None] + h * s["trend"][:, None] + s["season_hb"].gather(1, (h.clamp(max=HB) - 1))
+        if self.prophet:
+            f = pr_ref.forecast_state(s["level"], s["trend"], s["harm"], self.season, h)
+        else:
+            f = s["level"][:, None] + h * s["trend"][:, None] + s["season_hb"].gather(1, (h.clamp(max=HB) - 1))
         sigma = s["sigma"][:, None].expand_as(f)
-        if cfg.horizon_variance:
+        if cfg.horizon_variance and not self.prophet:
             best = s["best"].long()
             params = torch.where((best >= 0)[:, None], self.grid_all[best.clamp(min=0)],
                                  torch.zeros((best.shape[0], 3)))

@@ -204,3 +204,110 @@ def forecast_window(fit: ProphetWindowFit, horizons: torch.Tensor) -> torch.Tens
     if h.dim() == 1:
         return (fit.beta @ XH.T).to(torch.float32)
     return (XH * fit.beta[:, None, :]).sum(-1).to(torch.float32)
+
+
+# ---------------------------------------------------------------------------------
+# Harmonic forecast state (resident rollout engine, ops/csrc/prophet.hip)
+# ---------------------------------------------------------------------------------
+#
+# The rollout engine fits a row once, at admission, and scores it every tick at horizons
+# that grow with the job.  Past the window every hinge is active (cp_range < 1 puts every
+# changepoint inside it), so the model collapses to a line plus the Fourier terms with
+# their phase moved to the window's last sample:
+#
+#   f(h) = level + slope h + sum_j [ A_j sin(w_j h) + B_j cos(w_j h) ],   h = steps past T-1
+#   level = b0 + b1 + sum_k d_k (1 - c_k),   slope = (b1 + sum_k d_k) / (T - 1)
+#   w = 2 pi k / p,  th = w (T - 1 + phase):   A = a_s cos th - a_c sin th,  B = a_s sin th + a_c cos th
+#
+# A row of any window length has the same 16-float state, so rows fitted at different
+# geometries share one table and one scoring kernel.
+
+STATE_SEASONS = ((1, 4), (7, 3))     # (period in days, order): the seasons a window can enable
+STATE_HARM = 2 * sum(o for _, o in STATE_SEASONS)   # 14: daily A_1..4, B_1..4, weekly A_1..3, B_1..3
+
+
+def state_rotation(T: int, m: int, n_changepoints: int = 10, cp_range: float = 0.8, phase: float = 0.0):
+    """fp64 constants of :func:`window_state` for a (T, m) geometry: ``one_minus_c
+    [n_changepoints]``, and per harmonic (4 daily, 3 weekly) ``cos th`` / ``sin th`` ``[7]``
+    and whether its season is enabled ``[7]`` (bool)."""
+    if not cp_range < 1.0:
+        raise ValueError(f"cp_range {cp_range}: the forecast state needs every changepoint inside the window "
+                         "(cp_range < 1)")
+    if T < 2 or m < 2:
+        raise ValueError("the forecast state needs T >= 2 and m >= 2")
+    dt = torch.float64
+    cps = torch.arange(1, n_changepoints + 1, dtype=dt) / (n_changepoints + 1) * cp_range
+    enabled = {int(round(p)) for p, _ in window_seasons(T, m)}
+    cos, sin, on = [], [], []
+    for days, order in STATE_SEASONS:
+        p = days * m
+        for k in range(1, order + 1):
+            # th = 2 pi k (T - 1 + phase) / p, reduced before the multiplication by 2 pi
+            frac = math.fmod(k * (float(T - 1) + phase), float(p)) / float(p)
+            cos.append(math.cos(2 * math.pi * frac))
+            sin.append(math.sin(2 * math.pi * frac))
+            on.append(p in enabled)
+    return 1.0 - cps, torch.tensor(cos, dtype=dt), torch.tensor(sin, dtype=dt), torch.tensor(on)
+
+
+def state_from_beta(beta: torch.Tensor, T: int, m: int, n_changepoints: int = 10, cp_range: float = 0.8,
+                    phase: float = 0.0):
+    """``beta [N, P]`` of a window-scaled fit → ``level [N]``, ``slope [N]``, ``harm [N, 14]``
+    in fp64 (``harm``: daily ``A_1..4, B_1..4`` then weekly ``A_1..3, B_1..3``; zeros for a
+    season the window does not enable)."""
+    omc, cos, sin, on = state_rotation(T, m, n_changepoints, cp_range, phase)
+    b = beta.to(torch.float64)
+    dev = b.device
+    omc, cos, sin = omc.to(dev), cos.to(dev), sin.to(dev)
+    K = n_changepoints
+    delta = b[:, 2:2 + K]
+    level = b[:, 0] + b[:, 1] + (delta * omc[None, :]).sum(1)
+    slope = (b[:, 1] + delta.sum(1)) / float(T - 1)
+    harm = torch.zeros((b.shape[0], STATE_HARM), dtype=torch.float64, device=dev)
+    src, dst, j = 2 + K, 0, 0
+    for _days, order in STATE_SEASONS:
+        if bool(on[j]):
+            a_s, a_c = b[:, src:src + order], b[:, src + order:src + 2 * order]
+            c, s = cos[None, j:j + order], sin[None, j:j + order]
+            harm[:, dst:dst + order] = a_s * c - a_c * s
+            harm[:, dst + order:dst + 2 * order] = a_s * s + a_c * c
+            src += 2 * order
+        dst += 2 * order
+        j += order
+    return level, slope, harm
+
+
+def window_state(fit: ProphetWindowFit):
+    """Forecast state of a window-scaled fit: ``level [N]``, ``slope [N]`` (per sample),
+    ``harm [N, 14]`` in fp64.  ``forecast_state`` on it equals ``forecast_window(fit, h)``
+    for every ``h >= 0``.  Raises when ``fit.cp_range >= 1`` (a hinge would start past the
+    window and the trend would not be a line there)."""
+    return state_from_beta(fit.beta, fit.T, fit.m, fit.n_changepoints, fit.cp_range, fit.phase)
+
+
+def forecast_state(level: torch.Tensor, slope: torch.Tensor, harm: torch.Tensor, m: int,
+                   horizons: torch.Tensor) -> torch.Tensor:
+    """``level + slope h + sum_j [A_j sin(w_j h) + B_j cos(w_j h)]`` for ``horizons [C]`` or
+    ``[N, C]`` → ``[N, C]``, evaluated in fp64 and returned in ``level``'s dtype.  Integer
+    horizons have their phase reduced in integers (``(k h) mod p``), so the result does not
+    lose accuracy as ``h`` grows."""
+    dt = torch.float64
+    dev = level.device
+    h = horizons.to(dev)
+    if h.dim() == 1:
+        h = h[None, :]
+    exact = not (h.is_floating_point() or h.is_complex())
+    hf = h.to(dt)
+    out = level.to(dt)[:, None] + slope.to(dt)[:, None] * hf
+    hm = harm.to(dt)
+    dst = 0
+    for days, order in STATE_SEASONS:
+        p = days * int(m)
+        for k in range(1, order + 1):
+            if exact:
+                ang = (2 * math.pi / p) * torch.remainder(h.long() * k, p).to(dt)
+            else:
+                ang = (2 * math.pi * k / p) * hf
+            out = out + hm[:, dst + k - 1, None] * torch.sin(ang) + hm[:, dst + order + k - 1, None] * torch.cos(ang)
+        dst += 2 * order
+    return out.to(level.dtype)

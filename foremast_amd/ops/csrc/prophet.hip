@@ -20,6 +20,12 @@
 //   3. prophet_resid_kernel   lane = series: second pass over the window for sum r^2.
 //   4. prophet_detect_kernel  band / verdict epilogue, one 16-lane row per series.
 //
+// The resident rollout engine fits once per job and scores every tick at growing horizons:
+//   fm_prophet_fit_state     launches 1-3, then prophet_state_kernel (lane = series): the
+//                            forecast state level / slope / harm[14] from beta.
+//   fm_prophet_state_detect  prophet_state_detect_kernel: the band / verdict epilogue with the
+//                            forecast evaluated from the state at any horizon in 1..2^20.
+//
 // The tables are padded from P to PP in {12, 20, 26, 32} columns (zero features, unit
 // diagonal): the padded coefficients are exactly 0 and the inner loops unroll over PP.
 #include "args.h"
@@ -446,6 +452,124 @@ __global__ __launch_bounds__(256) void prophet_detect_kernel(const ProphetArgs a
   });
 }
 
+// ---- 5. harmonic forecast state (resident rollout engine) --------------------------------
+// Past the window every hinge is active, so the model is a line plus the Fourier terms with
+// their phase moved to the window's last sample (models/prophet_lite.py window_state):
+//   f(h) = level + slope h + sum_j [A_j sin(w_j h) + B_j cos(w_j h)].
+// A row of any window length has the same state, so rows fitted at different geometries are
+// scored by one launch.
+constexpr int PS_NH = 7;         // harmonics: 4 daily, 3 weekly
+constexpr int PS_HARM = 14;      // A_1..4, B_1..4 (daily), A_1..3, B_1..3 (weekly)
+constexpr int PS_TAB_CP = 16;    // table: [0] 1 / (T - 1), [1..7] cos th_j, [8..14] sin th_j, [16 + k] 1 - c_k
+constexpr int PS_HZ_MAX = 1 << 20;
+
+struct ProphetStateOut {
+  const float* tab;     // [16 + ncp] rotation table of the (T, m) geometry (fp64 on the host, cast)
+  float* level;         // [N]
+  float* slope;         // [N]
+  float* harm;          // [N, 14]
+  int ncp;              // changepoints
+  int nd;               // daily order in beta (4 or 0)
+  int nw;               // weekly order in beta (3 or 0)
+  int _pad;
+};
+
+struct ProphetStateArgs {
+  const float* level;   // [N]
+  const float* slope;   // [N]
+  const float* harm;    // [N, 14]
+  const float* sigma;   // [N]
+  const float* nvalid;  // [N]
+  int N;
+  int m;                // samples per day
+  DetectArgs det;
+};
+
+// lane = series: the rotation constants are wave-uniform (scalar) operands
+__global__ __launch_bounds__(256) void prophet_state_kernel(const float* __restrict__ beta, int PP, int N,
+                                                            const ProphetStateOut s) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const CF tab = as_const(s.tab);
+  const float* b = beta + (long long)n * PP;
+  const int K = s.ncp;
+  float lv = b[0] + b[1], ds = b[1];
+  for (int k = 0; k < K; ++k) {
+    const float d = b[2 + k];
+    lv = fmaf(d, tab[PS_TAB_CP + k], lv);
+    ds += d;
+  }
+  s.level[n] = lv;
+  s.slope[n] = ds * tab[0];
+  float* ho = s.harm + (long long)n * PS_HARM;
+  int src = 2 + K;
+  // daily (order 4) then weekly (order 3): beta holds sin 1..order, cos 1..order of an enabled season
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int order = q == 0 ? 4 : 3, on = q == 0 ? s.nd : s.nw, j0 = q == 0 ? 0 : 4, dst = q == 0 ? 0 : 8;
+#pragma unroll
+    for (int k = 0; k < order; ++k) {
+      float A = 0.f, B = 0.f;
+      if (on) {  // wave-uniform
+        const float as = b[src + k], ac = b[src + order + k];
+        const float c = tab[1 + j0 + k], sn = tab[1 + PS_NH + j0 + k];
+        A = fmaf(as, c, -(ac * sn));
+        B = fmaf(as, sn, ac * c);
+      }
+      ho[dst + k] = A;
+      ho[dst + order + k] = B;
+    }
+    src += on ? 2 * order : 0;
+  }
+}
+
+// sum_k [A_k sin(2 pi k h / p) + B_k cos(2 pi k h / p)], k = 1..ORDER, with the phase reduced in
+// integers: r_k = (k h) mod p by repeated addition of r_1 (h <= 2^20, p <= 7 * 86400: every
+// value fits 32 bits and converts to fp32 exactly), so the accuracy does not decay with h
+template <int ORDER>
+__device__ __forceinline__ float harm_sum(const float* hc, unsigned h, unsigned p) {
+  const unsigned r1 = h % p;
+  const float ip2 = 2.f / (float)p;
+  unsigned r = 0u;
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < ORDER; ++k) {
+    r += r1;
+    r -= r >= p ? p : 0u;
+    float sn, cs;
+    sincospif((float)r * ip2, &sn, &cs);
+    acc = fmaf(hc[k], sn, acc);
+    acc = fmaf(hc[ORDER + k], cs, acc);
+  }
+  return acc;
+}
+
+// band / verdict from the cached state, one 16-lane row per series (as prophet_detect_kernel)
+__global__ __launch_bounds__(256) void prophet_state_detect_kernel(const ProphetStateArgs a) {
+  const int n = blockIdx.x * (blockDim.x / 16) + (threadIdx.x >> 4);
+  if (n >= a.N) return;  // row-uniform
+  const float lv = a.level[n], sl = a.slope[n];
+  float hc[PS_HARM];
+  const float* hp = a.harm + (long long)n * PS_HARM;
+  float dmag = 0.f, wmag = 0.f;
+#pragma unroll
+  for (int k = 0; k < PS_HARM; ++k) {
+    hc[k] = hp[k];
+    if (k < 8) dmag += fabsf(hc[k]);
+    else wmag += fabsf(hc[k]);
+  }
+  // a season the row's window did not enable holds zeros (row-uniform: one series per row)
+  const bool daily = dmag != 0.f, weekly = wmag != 0.f;
+  const unsigned m = (unsigned)a.m;
+  detect_epilogue_row(a.det, n, a.sigma[n], a.nvalid[n], [&](int hz) {
+    const unsigned h = (unsigned)min(max(hz, 1), PS_HZ_MAX);
+    float f = fmaf(sl, (float)h, lv);
+    if (daily) f += harm_sum<4>(hc, h, m);
+    if (weekly) f += harm_sum<3>(hc + 8, h, 7u * m);
+    return f;
+  });
+}
+
 template <typename TIN, int PP>
 int launch_prophet(const ProphetArgs* a, hipStream_t st) {
   const int S = a->S;
@@ -483,13 +607,40 @@ int launch_prophet_pp(const ProphetArgs* a, hipStream_t st) {
 
 extern "C" long long fm_prophet_args_size() { return (long long)sizeof(ProphetArgs); }
 
+static bool prophet_fit_args_ok(const ProphetArgs* a) {
+  const int per16 = a->bf16 ? 8 : 4;
+  return !(a->T < 2 || a->T > a->ring_len || a->head < 0 || a->head >= a->ring_len || a->P < 1 || a->P > a->PP ||
+           a->S < 1 || a->S > 8 || a->ld < a->ring_len || a->ld % per16 != 0 ||
+           (((unsigned long long)a->hist) & 15ull) != 0 || !a->X || !a->A || !a->L || !a->LT || !a->reg ||
+           !a->XXp || !a->beta || !a->sigma || !a->nvalid || !a->mask || !a->defer);
+}
+
 extern "C" int fm_prophet_score(const ProphetArgs* a, hipStream_t st) {
   if (a->N <= 0) return 0;
-  const int per16 = a->bf16 ? 8 : 4;
-  if (a->T < 2 || a->T > a->ring_len || a->head < 0 || a->head >= a->ring_len || a->P < 1 || a->P > a->PP ||
-      a->hmax < 1 || a->hmax > 64 || a->S < 1 || a->S > 8 || a->ld < a->ring_len || a->ld % per16 != 0 ||
-      (((unsigned long long)a->hist) & 15ull) != 0 || !a->X || !a->XH || !a->A || !a->L || !a->LT || !a->reg ||
-      !a->XXp || !a->beta || !a->sigma || !a->nvalid || !a->mask || !a->defer)
-    return (int)hipErrorInvalidValue;
+  if (!prophet_fit_args_ok(a) || a->hmax < 1 || a->hmax > 64 || !a->XH) return (int)hipErrorInvalidValue;
   return a->bf16 ? launch_prophet_pp<bf16_t>(a, st) : launch_prophet_pp<float>(a, st);
+}
+
+extern "C" long long fm_prophet_state_out_size() { return (long long)sizeof(ProphetStateOut); }
+extern "C" long long fm_prophet_state_args_size() { return (long long)sizeof(ProphetStateArgs); }
+
+// The fit, gapped and residual launches of fm_prophet_score with no detection epilogue
+// (beta / sigma / nvalid are the same bits), then the forecast state of every series.
+extern "C" int fm_prophet_fit_state(const ProphetArgs* a, const ProphetStateOut* s, hipStream_t st) {
+  if (a->N <= 0) return 0;
+  if (!prophet_fit_args_ok(a) || a->det.C != 0 || !s->tab || !s->level || !s->slope || !s->harm || s->ncp < 0 ||
+      !(s->nd == 0 || s->nd == 4) || !(s->nw == 0 || s->nw == 3) || 2 + s->ncp + 2 * (s->nd + s->nw) != a->P)
+    return (int)hipErrorInvalidValue;
+  const int rc = a->bf16 ? launch_prophet_pp<bf16_t>(a, st) : launch_prophet_pp<float>(a, st);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(prophet_state_kernel, dim3((a->N + 255) / 256), dim3(256), 0, st, a->beta, a->PP, a->N, *s);
+  return (int)hipGetLastError();
+}
+
+extern "C" int fm_prophet_state_detect(const ProphetStateArgs* a, hipStream_t st) {
+  if (a->N <= 0 || a->det.C <= 0) return 0;
+  if (!a->level || !a->slope || !a->harm || !a->sigma || !a->nvalid || a->m < 2 || a->m > 86400)
+    return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(prophet_state_detect_kernel, dim3((a->N + 15) / 16), dim3(256), 0, st, *a);
+  return (int)hipGetLastError();
 }

@@ -9,6 +9,7 @@ HIP graph.
 
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -1097,9 +1098,31 @@ class ProphetArgs(C.Structure):
 nat.register("fm_prophet_score", [C.POINTER(ProphetArgs), C.c_void_p])
 nat.register("fm_prophet_args_size", [], C.c_longlong)
 
+
+class ProphetStateOut(C.Structure):
+    _fields_ = [("tab", C.c_void_p), ("level", C.c_void_p), ("slope", C.c_void_p), ("harm", C.c_void_p),
+                ("ncp", C.c_int), ("nd", C.c_int), ("nw", C.c_int), ("_pad", C.c_int)]
+
+
+class ProphetStateArgs(C.Structure):
+    _fields_ = [("level", C.c_void_p), ("slope", C.c_void_p), ("harm", C.c_void_p), ("sigma", C.c_void_p),
+                ("nvalid", C.c_void_p), ("N", C.c_int), ("m", C.c_int), ("det", nat.DetectArgs)]
+
+
+nat.register("fm_prophet_fit_state", [C.POINTER(ProphetArgs), C.POINTER(ProphetStateOut), C.c_void_p])
+nat.register("fm_prophet_state_detect", [C.POINTER(ProphetStateArgs), C.c_void_p])
+nat.register("fm_prophet_state_out_size", [], C.c_longlong)
+nat.register("fm_prophet_state_args_size", [], C.c_longlong)
+
 PROPHET_PAD = (12, 20, 26, 32)   # table widths the kernels are compiled for (P is padded up)
 PROPHET_HMAX = 64                # horizon rows of the forecast table
-_PROPHET_TABLES: Dict[tuple, Dict[str, object]] = {}
+PROPHET_HARM = 14                # harmonic coefficients of the forecast state (4 daily + 3 weekly, sin and cos)
+PROPHET_HZ_MAX = 1 << 20         # largest horizon the state kernel evaluates
+PROPHET_M_MAX = 86400            # samples per day (a 1 s step): 7 m and 4 * 2^20 stay inside 32 bits
+# geometries kept per device (least recently used first out): the rollout engine fits one
+# geometry per distinct number of dropped newest points, and XXp alone is 8.5 MB at T = 10,080
+PROPHET_TABLES_MAX = 8
+_PROPHET_TABLES: "collections.OrderedDict[tuple, Dict[str, object]]" = collections.OrderedDict()
 
 
 def prophet_tables(T: int, m: int, device, n_changepoints: int = 10, cp_range: float = 0.8,
@@ -1116,6 +1139,7 @@ def prophet_tables(T: int, m: int, device, n_changepoints: int = 10, cp_range: f
            else torch.cuda.current_device())
     tab = _PROPHET_TABLES.get(key)
     if tab is not None:
+        _PROPHET_TABLES.move_to_end(key)
         return tab
     from ..models import prophet_lite as pl
     X, XH, reg, A = pl.design_window(int(T), int(m), PROPHET_HMAX, n_changepoints, cp_range, ridge_cp, ridge)
@@ -1143,7 +1167,21 @@ def prophet_tables(T: int, m: int, device, n_changepoints: int = 10, cp_range: f
     tab = {"P": P, "PP": PP, "X": Xp.to(**f32), "XXp": XXp.to(**f32), "XH": pad(XH, PROPHET_HMAX).to(**f32),
            "A": Ap.to(**f32), "L": L.contiguous().to(**f32), "LT": L.T.contiguous().to(**f32),
            "reg": regp.to(**f32)}
+    if cp_range < 1.0:  # rotation constants of the forecast state (prophet.hip prophet_state_kernel)
+        omc, cos, sin, on = pl.state_rotation(int(T), int(m), n_changepoints, cp_range)
+        st = torch.zeros(16 + int(n_changepoints), dtype=dt)
+        st[0] = 1.0 / float(int(T) - 1)
+        st[1:8], st[8:15], st[16:] = cos, sin, omc
+        tab.update(state=st.to(**f32), ncp=int(n_changepoints), nd=4 if bool(on[0]) else 0,
+                   nw=3 if bool(on[4]) else 0)
     _PROPHET_TABLES[key] = tab
+    # a caller holding an evicted geometry's tables keeps them alive until its launches are queued;
+    # the allocator reuses their memory in stream order.  (No fit is captured into a HIP graph:
+    # the shards capture only Holt-Winters ticks and the rollout engine fits eagerly at admission;
+    # a capture would have to keep its own reference to the tables.)
+    on_dev = [k for k in _PROPHET_TABLES if k[-2:] == key[-2:]]
+    for k in on_dev[:max(0, len(on_dev) - PROPHET_TABLES_MAX)]:
+        del _PROPHET_TABLES[k]
     return tab
 
 
@@ -1159,22 +1197,39 @@ def prophet_score(hist: torch.Tensor, head: int, length: int, m: int, det: Detec
     ``sigma`` / ``nvalid`` ``[N]``, the detection outputs, and ``beta [N, P]`` (a view of
     the workspace) with ``want_beta``."""
     lib = nat.require()
-    _hist_check(hist, head, length)
-    _need(length >= 2, f"window of {length} samples: prophet needs at least 2")
-    _need(int(m) >= 2, f"period {m}: prophet needs m >= 2")
-    bf16 = hist.dtype == torch.bfloat16
-    _need(hist.stride(0) % (8 if bf16 else 4) == 0 and hist.data_ptr() % 16 == 0,
-          "hist rows must be 16-byte aligned for vector loads")
+    _prophet_hist_check(hist, head, length, m)
     hmax = det.max_horizon
     if hmax is None:
         hmax = int(det.horizons.max()) if det.horizons.numel() else 1  # one sync: pass max_horizon per tick
     _need(1 <= int(hmax) <= PROPHET_HMAX, f"horizons up to {hmax}: the prophet kernel takes 1..{PROPHET_HMAX}")
     N, dev = hist.shape[0], hist.device
     tab = prophet_tables(length, m, dev, n_changepoints, cp_range, ridge_cp, ridge)
+    out = {} if out is None else out
+    a = _prophet_fit_args(hist, head, length, tab, out)
+    _fill_detect(a.det, det, N, dev, out)
+    nat.check(lib.fm_prophet_score(C.byref(a), nat.stream_handle(dev)), "fm_prophet_score")
+    if want_beta:
+        out["beta"] = out["_beta"][:, :tab["P"]]
+    return out
+
+
+def _prophet_hist_check(hist: torch.Tensor, head: int, length: int, m: int) -> None:
+    _hist_check(hist, head, length)
+    _need(length >= 2, f"window of {length} samples: prophet needs at least 2")
+    _need(int(m) >= 2, f"period {m}: prophet needs m >= 2")
+    bf16 = hist.dtype == torch.bfloat16
+    _need(hist.stride(0) % (8 if bf16 else 4) == 0 and hist.data_ptr() % 16 == 0,
+          "hist rows must be 16-byte aligned for vector loads")
+
+
+def _prophet_fit_args(hist: torch.Tensor, head: int, length: int, tab: Dict[str, object],
+                      out: Dict[str, torch.Tensor]) -> ProphetArgs:
+    """Outputs / workspaces of the fit launches in ``out`` and their argument block (the
+    detection part left zero: no epilogue)."""
+    N, dev = hist.shape[0], hist.device
     P, PP = tab["P"], tab["PP"]
     R = hist.shape[1]
     Q = (R + 31) // 32
-    out = {} if out is None else out
     f32 = dict(dtype=torch.float32, device=dev)
     for k in ("sigma", "nvalid"):
         if k not in out:
@@ -1188,15 +1243,77 @@ def prophet_score(hist: torch.Tensor, head: int, length: int, m: int, det: Detec
         out["_defer"] = torch.zeros(N + 1, dtype=torch.int32, device=dev)
     a = ProphetArgs()
     a.hist, a.ld, a.ring_len, a.head, a.T, a.N = nat.ptr(hist), hist.stride(0), R, int(head), int(length), N
-    a.bf16, a.P, a.PP, a.hmax = int(bf16), P, PP, PROPHET_HMAX
+    a.bf16, a.P, a.PP, a.hmax = int(hist.dtype == torch.bfloat16), P, PP, PROPHET_HMAX
     a.X, a.XH, a.A, a.L, a.LT, a.reg, a.XXp = (nat.ptr(tab[k]) for k in ("X", "XH", "A", "L", "LT", "reg", "XXp"))
     a.beta, a.sigma, a.nvalid = nat.ptr(out["_beta"]), nat.ptr(out["sigma"]), nat.ptr(out["nvalid"])
     a.mask, a.defer = nat.ptr(out["_mask"]), nat.ptr(out["_defer"])
     a.S = max(1, min(8, Q))
-    _fill_detect(a.det, det, N, dev, out)
-    nat.check(lib.fm_prophet_score(C.byref(a), nat.stream_handle(dev)), "fm_prophet_score")
+    return a
+
+
+def prophet_fit_state(hist: torch.Tensor, head: int, length: int, m: int,
+                      out: Optional[Dict[str, torch.Tensor]] = None, n_changepoints: int = 10,
+                      cp_range: float = 0.8, ridge_cp: float = 10.0, ridge: float = 1e-4,
+                      want_beta: bool = False) -> Dict[str, torch.Tensor]:
+    """Admission fit of the resident rollout engine: the fit of :func:`prophet_score` (same
+    ``sigma`` / ``nvalid`` / ``beta`` bits, no detection epilogue) reduced to the forecast
+    state ``level [N]``, ``slope [N]`` (per sample), ``harm [N, 14]`` (models/prophet_lite.py
+    ``window_state``), which :func:`prophet_state_detect` scores at any horizon.  Needs
+    ``cp_range < 1`` (every hinge active past the window)."""
+    lib = nat.require()
+    _prophet_hist_check(hist, head, length, m)
+    _need(int(m) <= PROPHET_M_MAX, f"period {m}: the state kernel takes m <= {PROPHET_M_MAX}")
+    _need(float(cp_range) < 1.0, f"cp_range {cp_range}: the forecast state needs cp_range < 1")
+    N, dev = hist.shape[0], hist.device
+    tab = prophet_tables(length, m, dev, n_changepoints, cp_range, ridge_cp, ridge)
+    out = {} if out is None else out
+    a = _prophet_fit_args(hist, head, length, tab, out)
+    f32 = dict(dtype=torch.float32, device=dev)
+    for k, shape in (("level", (N,)), ("slope", (N,)), ("harm", (N, PROPHET_HARM))):
+        if k not in out:
+            out[k] = torch.empty(shape, **f32)
+        else:
+            t = out[k]
+            _need(tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev,
+                  f"out[{k!r}] must be contiguous float32 {list(shape)} on {dev}")
+    s = ProphetStateOut()
+    s.tab, s.level, s.slope, s.harm = (nat.ptr(t) for t in (tab["state"], out["level"], out["slope"], out["harm"]))
+    s.ncp, s.nd, s.nw = tab["ncp"], tab["nd"], tab["nw"]
+    nat.check(lib.fm_prophet_fit_state(C.byref(a), C.byref(s), nat.stream_handle(dev)), "fm_prophet_fit_state")
     if want_beta:
-        out["beta"] = out["_beta"][:, :P]
+        out["beta"] = out["_beta"][:, :tab["P"]]
+    return out
+
+
+def prophet_state_detect(state: Dict[str, torch.Tensor], m: int, det: DetectSpec,
+                         out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """Band / verdict / per-app counters / K9 list / per-row record of every row from its
+    cached prophet state (``level``, ``slope``, ``harm [N, 14]``, ``sigma``, ``nvalid`` of
+    :func:`prophet_fit_state`) at the horizons of ``det`` (shared ``[C]`` or per-row ``[N, C]``,
+    values in 1..2^20), with sigma the residual standard deviation (no horizon factor).  One
+    launch, stream-ordered, no host synchronisation.  ``m``: samples per day."""
+    lib = nat.require()
+    for kname in ("level", "slope", "harm", "sigma", "nvalid"):
+        _need(kname in state, f"prophet state needs state[{kname!r}] from the fit")
+    lvl = state["level"]
+    _cuda(lvl, "state['level']")
+    _need(lvl.dim() == 1, f"state['level'] must be [N], got {tuple(lvl.shape)}")
+    N, dev = lvl.shape[0], lvl.device
+    for kname in ("level", "slope", "sigma", "nvalid"):
+        _vec(state[kname], N, torch.float32, f"state[{kname!r}]", dev)
+    h = state["harm"]
+    _need(h.dim() == 2 and tuple(h.shape) == (N, PROPHET_HARM) and h.dtype == torch.float32 and h.is_contiguous()
+          and h.device == dev, f"state['harm'] must be contiguous float32 [{N}, {PROPHET_HARM}] on {dev}")
+    _need(2 <= int(m) <= PROPHET_M_MAX, f"period {m}: the state kernel takes 2 <= m <= {PROPHET_M_MAX}")
+    if det.max_horizon is not None:
+        _need(1 <= int(det.max_horizon) <= PROPHET_HZ_MAX,
+              f"horizons up to {det.max_horizon}: the state kernel takes 1..{PROPHET_HZ_MAX}")
+    out = {} if out is None else out
+    a = ProphetStateArgs()
+    a.level, a.slope, a.harm = nat.ptr(lvl), nat.ptr(state["slope"]), nat.ptr(h)
+    a.sigma, a.nvalid, a.N, a.m = nat.ptr(state["sigma"]), nat.ptr(state["nvalid"]), N, int(m)
+    _fill_detect(a.det, det, N, dev, out)
+    nat.check(lib.fm_prophet_state_detect(C.byref(a), nat.stream_handle(dev)), "fm_prophet_state_detect")
     return out
 
 
