@@ -1152,6 +1152,397 @@ __device__ __forceinline__ int hint_pair_at(int k, int lo, unsigned hp) {
   return r;
 }
 
+// ---- variant 5: what hw_d_block, hw_q_block and hw_dg_block share ---------------------------
+// A workgroup fits S series, one per group of 64 / S lanes of every wave (S = 2: 32 lanes x
+// K steps, S = 4: 16 lanes x K steps).  Shared by the two dense blocks: the LDS layout, staging,
+// the initial state, the hint pairs, the set-up of a grid pair, the best-candidate update, the
+// queue and the finish; each keeps its own grid loop (the scan flavour and the split tail tell
+// them apart).  hw_dg_block takes the layout and the LDS / hint set-up from here and keeps its
+// own copy of the rest: see there.
+
+// LDS of a workgroup with ns1 fitted seasons, in 4-byte words.  The kernels take their
+// pointers from it and fm_hw_{d,q,dg}_lds_bytes their sizes:
+//   dl[S][ns1][SEA] | vmask[S][NMW] | stat[waves][S][4] | flag[4] | ylast[S][HB] |
+//   bests[waves][S][HB] | wbest[waves][S][4] | ubound[S bounds, queue, hint pairs, pad]
+// and, for the gapped kernel (S = 2), mbits[2][ns1][32][2] | segm[2][ns1] | nvc[2]: the
+// per-(series, season, lane) 64-bit miss masks, per-(series, season) gap flags and the two
+// valid-point counts.
+template <int K, int S>
+struct DLds {
+  static constexpr int SEA = DLay<K>::SEASON;
+  static constexpr int NMW = ((64 / S) * K + 31) / 32;          // season-0 validity bitmask words per series
+  static constexpr int ZEROED = S * NMW + 4 * S * D_WAVES + 4;  // vmask, stat, flag: cleared together
+  static constexpr int QUEUE = S, HINTS = S + 1;                // ubound slots after the S per-series SSE bounds
+  static constexpr int UBOUND = (S + 2 + 3) & ~3;
+  static constexpr int FIXED = ZEROED + S * HALF_HB + D_WAVES * S * HALF_HB + D_WAVES * S * 4 + UBOUND;
+  __host__ __device__ static constexpr size_t words(int ns1) { return (size_t)S * ns1 * SEA + FIXED; }
+  __host__ __device__ static constexpr size_t gap_words(int ns1) { return (size_t)2 * ns1 * 64 + 2 * ns1 + 2; }
+
+  float* dl;
+  unsigned* vmask;
+  float* stat;
+  int* flag;
+  float* ylast;
+  float* bests;
+  float* wbest;
+  unsigned* ubound;
+  unsigned* mbits;  // the gapped extension (inside the allocation of hw_dg_kernel only)
+  int* segm;
+  float* nvc;
+  __device__ __forceinline__ explicit DLds(int ns1) {
+    dl = (float*)fm_hw_smem;
+    vmask = (unsigned*)(dl + (size_t)S * ns1 * SEA);
+    stat = (float*)(vmask + S * NMW);
+    flag = (int*)(stat + 4 * S * D_WAVES);
+    ylast = (float*)(flag + 4);
+    bests = ylast + S * HALF_HB;
+    wbest = bests + D_WAVES * S * HALF_HB;
+    ubound = (unsigned*)(wbest + D_WAVES * S * 4);
+    mbits = ubound + UBOUND;
+    segm = (int*)(mbits + 2 * ns1 * 64);
+    nvc = (float*)(segm + 2 * ns1);
+  }
+};
+
+// f(0), ..., f(N - 1) with the index a compile-time constant (std::integral_constant).  The
+// per-series arrays below are indexed through it only: indexed by an unrolled loop's variable
+// they are still arrays when the loop is unrolled, and the `if (q == r)` updates were then
+// merged into one dynamically indexed update: private memory, i.e. scratch.
+template <int N, int I = 0, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>());
+    static_for<N, I + 1>(f);
+  }
+}
+
+// element sid of a per-series array, by selects
+template <int S>
+__device__ __forceinline__ float pick(const float (&v)[S], int sid) {
+  float r = v[0];
+  static_for<S>([&](auto q) __attribute__((always_inline)) { r = sid == q ? v[q] : r; });
+  return r;
+}
+
+// sums and counts of the observed points of seasons 0 and 1 (for l0 and b0)
+struct SeasonSums {
+  float s0, c0, s1, c1;
+  __device__ __forceinline__ void add(const SeasonSums& o) { s0 += o.s0; c0 += o.c0; s1 += o.s1; c1 += o.c1; }
+  // add(o) if `on`, as selects: the sums start at +0 and never become -0, so adding +0 is
+  // exact (the quad kernel's conditional update of one of four sums was merged into a
+  // dynamically indexed one: scratch)
+  __device__ __forceinline__ void add_if(bool on, const SeasonSums& o) {
+    s0 += on ? o.s0 : 0.f; c0 += on ? o.c0 : 0.f; s1 += on ? o.s1 : 0.f; c1 += on ? o.c1 : 0.f;
+  }
+};
+
+// Clears vmask / stat / flag, sets the bounds to +inf and the queue to 0, and packs the hint
+// pairs: the grid pairs inside [lo, hi) that won the previous fit of series n0 and n0 + 1
+// (a.best still holds it: only this block -- or, split, the second arriver of its two
+// halves -- rewrites it, at the end) go first, so the branch and bound starts from a
+// near-optimal bound (exact in any order)
+template <int K, int S>
+__device__ __forceinline__ void d_lds_init(const DLds<K, S>& L, const SmoothArgs& a, int tid, int n0, int hints,
+                                           int lo, int hi) {
+  for (int i = tid; i < L.ZEROED; i += blockDim.x) L.vmask[i] = 0u;
+  if (tid < S + 1) L.ubound[tid] = tid < S ? 0x7f800000u : 0u;
+  if (tid == S + 1) {
+    unsigned hp[2] = {0xffffu, 0xffffu};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int b = (hints && n0 + r < a.N) ? a.best[n0 + r] : -1;
+      const int q = (b >= 0 && b < a.G) ? b / 2 : -1;
+      if (q >= lo && q < hi && (r == 0 || (unsigned)q != hp[0])) hp[r] = (unsigned)q;
+    }
+    L.ubound[L.HINTS] = hp[0] | (hp[1] << 16);
+  }
+}
+
+// Staging load: all seasons of 8 consecutive phases (from o0) of one series into y, every
+// load in flight before the first wait.  Aligned rings (`al`: R, m, ld multiples of 8, 16-B
+// row base; o0 shifted so that each season's 8 columns are one aligned 16-byte chunk): one
+// load per season, no per-element address math; otherwise one clamped 2-byte load per
+// element.  Padding (before the series' start) is NaN; the padding series of a short last
+// group (!real) is zeros, which keeps the group on the fast path.
+__device__ __forceinline__ void stage_load(const bf16_t* row, bool real, bool al, int o0, int head, int nseg, int m,
+                                           int R, int pad, float (&y)[D_MAXSEG][8]) {
+  if (al) {
+#pragma unroll
+    for (int k = 0; k < D_MAXSEG; ++k) {
+      const int t0 = k * m + o0 - pad;  // logical index of element 0 (multiple-of-8 column)
+      int c = (head + t0) % R;
+      c += c < 0 ? R : 0;
+      uint4 w = make_uint4(0u, 0u, 0u, 0u);
+      if (k < nseg) w = *(const uint4*)(row + c);  // k < nseg is block-uniform
+      const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const unsigned x = ww[u >> 1];
+        const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
+        const bool ok = real && k < nseg;
+        y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < D_MAXSEG; ++k) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        // branch-free: every load is issued (clamped to a valid column) and the value
+        // selected afterwards
+        const bool ok = real && k < nseg && o0 + u < m;
+        const int t = k * m + o0 + u - pad;
+        const bool pos = t >= 0;
+        int c = head + ((ok && pos) ? t : 0);
+        c -= (c >= R) ? R : 0;
+        const float v = bf16_to_f32(row[c]);
+        y[k][u] = ok ? (pos ? v : fm_nan()) : 0.f;
+      }
+    }
+  }
+}
+
+// Staging scatter of one loaded group (series r of the workgroup, phases o0 .. o0 + 7): the
+// season differences into the dl image, the season-0 validity bits (at most two atomicOr),
+// the newest season's first phases into ylast, and the season-0 / season-1 sums and counts
+// into acc[r].  A NaN in a season k >= 1 sets `bad` (the pair then goes to the gapped kernel).
+template <int K, int S>
+__device__ __forceinline__ void stage_scatter(const DLds<K, S>& L, int nseg, int m, int r, int o0,
+                                              float (&y)[D_MAXSEG][8], SeasonSums (&acc)[S], int& bad) {
+  constexpr int SEA = DLds<K, S>::SEA, NMW = DLds<K, S>::NMW;
+  const int ns1 = nseg - 1;
+  // (lane, step) of the group's first in-range phase; later phases step from it
+  const int ob = o0 > 0 ? o0 : 0;
+  const int jjb = ob / K, ib = ob - jjb * K;
+  unsigned vlo = 0u, vhi = 0u;  // season-0 validity bits for words ob >> 5 and (ob >> 5) + 1
+  SeasonSums grp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int o = o0 + u;
+    if (o >= 0 && o < m) {
+      int i = ib + (o - ob), jj = jjb;
+      if (i >= K) { i -= K; ++jj; }
+      const bool v0 = y[0][u] == y[0][u];
+      const bool v1 = y[1][u] == y[1][u];
+#pragma unroll
+      for (int k = 1; k < D_MAXSEG; ++k)
+        if (k < nseg && y[k][u] != y[k][u]) bad = 1;
+      float* blk = L.dl + (size_t)r * ns1 * SEA + dl_off(i, jj);
+      blk[0] = v0 ? y[1][u] - y[0][u] : y[1][u];  // D^(1) = y1 - s0; + l0 for valid y0 once the means are known
+      if (v0) {
+        if ((o >> 5) == (ob >> 5)) vlo |= 1u << (o & 31);
+        else vhi |= 1u << (o & 31);
+      }
+#pragma unroll
+      for (int k = 1; k < D_MAXSEG - 1; ++k)
+        if (k < ns1) blk[(size_t)k * SEA] = y[k + 1][u] - y[k][u];
+      if (o < HALF_HB) {
+        float yl = y[1][u];
+#pragma unroll
+        for (int k = 2; k < D_MAXSEG; ++k)
+          if (k == ns1) yl = y[k][u];
+        L.ylast[r * HALF_HB + o] = yl;
+      }
+      // observed points only (an imputed value is not data)
+      const SeasonSums t = {v0 ? y[0][u] : 0.f, v0 ? 1.f : 0.f, v1 ? y[1][u] : 0.f, v1 ? 1.f : 0.f};
+      // Summation order, kept per kernel so that l0 / b0 stay bit-identical: the 32-lane
+      // kernels add every element straight into the series' sums, the quad kernel sums the
+      // group first and then adds the group's sum.
+      if constexpr (S == 4) {
+        grp.add(t);
+      } else {
+        static_for<S>([&](auto q) __attribute__((always_inline)) {
+          if (q == r) acc[q].add(t);
+        });
+      }
+    }
+  }
+  if constexpr (S == 4) {
+    static_for<S>([&](auto q) __attribute__((always_inline)) { acc[q].add_if(q == r, grp); });
+  }
+  if (vlo) atomicOr(&L.vmask[r * NMW + (ob >> 5)], vlo);
+  if (vhi) atomicOr(&L.vmask[r * NMW + (ob >> 5) + 1], vhi);
+}
+
+// Stage phase: one thread per (series, 8 consecutive phases), all seasons of them in flight
+// at once; then the season-0 / season-1 sums and counts of each series to this wave's stat
+// slots.  The slots are summed in wave order (d_means): a float atomicAdd's order would make
+// l0 / b0 (and a beta = 0 fit's trend) differ in the last bit from run to run.
+template <int K, int S>
+__device__ __forceinline__ void d_stage(const DLds<K, S>& L, const SmoothArgs& a, int n0, int head, int tid, int lane,
+                                        int w, int& bad) {
+  constexpr int GRP = 8;
+  const int nseg = a.Tp / a.seg, m = a.m, R = a.ring_len;
+  const bool al = (R % GRP == 0) && (m % GRP == 0) && (a.ld % GRP == 0) &&
+                  ((((unsigned long long)a.hist) & 15ull) == 0);
+  // aligned: the phase groups are shifted by phi = (pad - head) mod 8
+  const int phi = al ? (((a.pad - head) % GRP) + GRP) % GRP : 0;
+  const int ostart = phi ? phi - GRP : 0;
+  const int ngrp = (m - ostart + GRP - 1) / GRP;
+  SeasonSums acc[S];
+  static_for<S>([&](auto q) __attribute__((always_inline)) { acc[q] = {0.f, 0.f, 0.f, 0.f}; });
+  for (int g = tid; g < S * ngrp; g += blockDim.x) {
+    const int r = S == 2 ? (g >= ngrp ? 1 : 0) : g / ngrp;  // two series: a compare is enough
+    const int o0 = ostart + (g - r * ngrp) * GRP;
+    const int n = n0 + r;
+    const bool real = n < a.N;
+    const bf16_t* row = (const bf16_t*)a.hist + (long long)(real ? n : 0) * a.ld;
+    float y[D_MAXSEG][GRP];
+    stage_load(row, real, al, o0, head, nseg, m, R, a.pad, y);
+    stage_scatter(L, nseg, m, r, o0, y, acc, bad);
+  }
+  static_for<S>([&](auto q) __attribute__((always_inline)) {
+    acc[q] = {wave_sum(acc[q].s0), wave_sum(acc[q].c0), wave_sum(acc[q].s1), wave_sum(acc[q].c1)};
+  });
+  if (lane == 0) {
+    static_for<S>([&](auto q) __attribute__((always_inline)) {
+      float* sw = L.stat + 4 * S * w + 4 * q;
+      sw[0] = acc[q].s0; sw[1] = acc[q].c0; sw[2] = acc[q].s1; sw[3] = acc[q].c1;
+    });
+  }
+}
+
+// Initial state of each series from the stat slots (l0: mean of season 0, b0: the step from
+// it to the mean of season 1, per sample), then D^(1) = y1 - s0 with s0 = y0 - l0 where y0
+// is valid (0 elsewhere).  The caller synchronises before the image is read.
+template <int K, int S>
+__device__ __forceinline__ void d_means(const DLds<K, S>& L, int m, int ns1, int tid, float (&l0r)[S],
+                                        float (&b0r)[S]) {
+  static_for<S>([&](auto r) __attribute__((always_inline)) {
+    SeasonSums st = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int v = 0; v < D_WAVES; ++v) {
+      const float* sw = L.stat + 4 * S * v + 4 * r;
+      st.add({sw[0], sw[1], sw[2], sw[3]});
+    }
+    l0r[r] = st.c0 > 0.f ? st.s0 / st.c0 : 0.f;
+    b0r[r] = ((st.c1 > 0.f ? st.s1 / st.c1 : 0.f) - l0r[r]) / (float)m;
+  });
+  // series by series: no division by m, and every element is still touched exactly once
+  static_for<S>([&](auto r) __attribute__((always_inline)) {
+    for (int o = tid; o < m; o += blockDim.x) {
+      if ((L.vmask[r * L.NMW + (o >> 5)] >> (o & 31)) & 1u) {
+        const int jj = o / K, i = o - jj * K;
+        L.dl[(size_t)r * ns1 * L.SEA + dl_off(i, jj)] += l0r[r];
+      }
+    }
+  });
+}
+
+// One grid pair's constants: the two grid indices (the second repeats the first past an odd
+// grid's end), c1 / c2 / g1a, the pass-1 weight and scan tables, B^1, B^2, B^4, B^8 of the
+// next scan and Bj = B^(lane & 15)
+template <int K>
+struct GridPair {
+  int c0, c1i;
+  cfp W, tb;
+  v2f c1, c2, g1a;
+  Mat2 Bj, Bp[4];
+  __device__ __forceinline__ GridPair(const SmoothArgs& a, int pi, int lane) {
+    c0 = 2 * pi;
+    c1i = (2 * pi + 1 < a.G) ? 2 * pi + 1 : c0;
+    const cfp tab = const_ptr(a.pair_tab + (size_t)pi * PairTab<K>::SIZE);
+    c1 = ldv2(tab); c2 = ldv2(tab + 2); g1a = ldv2(tab + 4);
+    W = tab + PairTab<K>::W0;
+    tb = tab + PairTab<K>::B0;
+    const v2f one = splat2(1.f), zero = splat2(0.f);
+    Bj.a = one; Bj.b = zero; Bj.c = zero; Bj.d = one;
+#pragma unroll
+    for (int bit = 0; bit < 4; ++bit) Bp[bit] = ldmat(tb + 8 * bit);
+    fence_sched();  // all four requested before the first is used: one scalar-cache wait, not four
+#pragma unroll
+    for (int bit = 0; bit < 4; ++bit) {
+      const Mat2 r = matmul(Bj, Bp[bit]);
+      if ((lane >> bit) & 1) Bj = r;
+    }
+  }
+};
+
+// a lane group's best grid point so far
+struct Best {
+  float sse;
+  int idx;
+  float L, B;
+};
+
+// A finished grid pair against the group's best: the smaller SSE wins, a tie goes to the
+// smaller grid index.  `phases(upd1)` stores the winner's seasonal phases (which lanes write
+// is the caller's); then the group's first lane publishes the bound (SSE >= 0: float order is
+// unsigned-int order; a NaN never lowers it).
+template <bool PRUNE, typename Phases>
+__device__ __forceinline__ void take_candidate(Best& b, v2f sse, v2f X1, v2f X2, int c0, int c1i, bool first,
+                                               unsigned* ubp, Phases&& phases) {
+  const bool upd0 = (sse.x < b.sse || (sse.x == b.sse && c0 < b.idx));
+  if (upd0) { b.sse = sse.x; b.idx = c0; b.L = X1.x - X2.x; b.B = X2.x; }
+  const bool upd1 = (c1i != c0) && (sse.y < b.sse || (sse.y == b.sse && c1i < b.idx));
+  if (upd1) { b.sse = sse.y; b.idx = c1i; b.L = X1.y - X2.y; b.B = X2.y; }
+  if (upd0 || upd1) phases(upd1);
+  if (PRUNE && first && (upd0 || upd1))
+    __hip_atomic_fetch_min(ubp, __float_as_uint(b.sse), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// the dense kernels' `phases`: the forecast's phases 0 .. hmax - 1 (hmax <= K) are lane 0's
+template <int K>
+__device__ __forceinline__ void first_lane_phases(float* mybest, const float* yl, const v2f* D, bool upd1, int j,
+                                                  int hmax) {
+  if (j == 0) {
+#pragma unroll
+    for (int i = 0; i < K && i < HALF_HB; ++i)
+      if (i < hmax) mybest[i] = yl[i] - (upd1 ? D[i].y : D[i].x);
+  }
+}
+
+// the wave's next position in the block's pair queue: the first round is static (w), later
+// ones come from the queue
+__device__ __forceinline__ int queue_pop(unsigned* queue, int lane, int nwaves) {
+  int q = 0;
+  if (lane == 0) q = __hip_atomic_fetch_add(queue, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  return nwaves + __builtin_amdgcn_readfirstlane(q);
+}
+
+// arg-min across the waves: each lane group leaves its best in wbest[w][sid] ...
+template <int S>
+__device__ __forceinline__ void put_wave_best(float* wbest, int w, int sid, const Best& b) {
+  float* wb = wbest + (w * S + sid) * 4;
+  wb[0] = b.sse;
+  wb[1] = __int_as_float(b.idx);
+  wb[2] = b.L;
+  wb[3] = b.B;
+}
+// ... and the wave that finishes series r picks the winner (same tie rule)
+template <int S>
+__device__ __forceinline__ int wave_argmin(const float* wbest, int r, int nwaves) {
+  int win = 0;
+  for (int q = 1; q < nwaves; ++q) {
+    const float sq = wbest[(q * S + r) * 4], sw = wbest[(win * S + r) * 4];
+    const int iq = __float_as_int(wbest[(q * S + r) * 4 + 1]), iw = __float_as_int(wbest[(win * S + r) * 4 + 1]);
+    if (sq < sw || (sq == sw && iq < iw)) win = q;
+  }
+  return win;
+}
+
+// One wave writes series n's fit (sb: its HALF_HB best seasonal phases in LDS, nvr: its
+// valid points past season 0) and runs the detection epilogue
+__device__ __forceinline__ void finish_series(const SmoothArgs& a, int n, int lane, int hmax, float gSSE, int gIdx,
+                                              float gL, float gB, const float* sb, float nvr) {
+  const float sig = sqrtf(gSSE / fmaxf(nvr, 1.f));
+  if (lane == 0) {
+    a.level[n] = gL;
+    a.trend[n] = gB;
+    a.sigma[n] = sig;
+    a.best[n] = gIdx;
+  }
+  const int Tp = a.Tp, m = a.m;
+  if (a.season_hb && lane < hmax) a.season_hb[(long long)n * HALF_HB + lane] = sb[lane];
+  if (a.nvalid_out && lane == 0) a.nvalid_out[n] = nvr;
+  detect_epilogue_wave(a.det, n, sig, nvr, [&](int h) {
+    int ph = (Tp - 1 + h) % m;
+    if (ph < 0) ph += m;
+    ph = ph < HALF_HB ? ph : HALF_HB - 1;  // host guarantees ph < hmax; clamp keeps LDS reads in bounds
+    return gL + (float)h * gB + sb[ph];
+  }, gIdx);
+}
+
 // Split tail (see fm_hw_d_fit): a workgroup may fit only the grid pairs [pi_lo, pi_hi)
 // of its series pair; its per-series best then goes to slot `slot` of `cand` (half
 // `hid`), and whichever half arrives second merges the two and finishes the series.
@@ -1160,25 +1551,13 @@ constexpr int CAND_FLOATS = 4 + HALF_HB;  // SSE, index bits, level, trend, seas
 template <int K, bool PRUNE>
 __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0, int* deferred, int pi_lo,
                                            int pi_hi, int slot, int hid, int* cnt, float* cand, int hints) {
-  constexpr int SEA = DLay<K>::SEASON;
-  constexpr int TS = PairTab<K>::SIZE;
-  constexpr int NMW = (32 * K + 31) / 32;  // season-0 validity bitmask words per series
+  using Lds = DLds<K, 2>;
+  constexpr int SEA = Lds::SEA;
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
   const int half = lane >> 5, j = lane & 31;
   const bool odd_row = ((lane >> 4) & 1) != 0;
   const int nseg = a.Tp / a.seg, m = a.m, ns1 = nseg - 1;
-
-  // ---- LDS: dl[2][ns1][SEA] | vmask[2][NMW] | stat[4 waves][2][4] | flag | ylast[2][HB] | bests[4][2][HB] | wbest[4][2][4]
-  //          | ubound[4]
-  float* dl = (float*)fm_hw_smem;
-  unsigned* vmask = (unsigned*)(dl + (size_t)2 * ns1 * SEA);
-  float* stat = (float*)(vmask + 2 * NMW);
-  int* flag = (int*)(stat + 8 * D_WAVES);
-  float* ylast = (float*)(flag + 4);
-  float* bests = ylast + 2 * HALF_HB;
-  float* wbest = bests + 4 * 2 * HALF_HB;
-  // [0..1] per-series SSE bound, [2] pair queue, [3] hint pairs (lo16 | hi16, 0xffff = none)
-  unsigned* ubound = (unsigned*)(wbest + 4 * 2 * 4);
+  const Lds L(ns1);
 
   // a pair the gapped kernel took in the last fit (its gap is almost always still in the
   // window: the ring moved a few columns) goes straight back to it, without staging here
@@ -1190,134 +1569,15 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
     }
     return;
   }
-  for (int i = tid; i < 2 * NMW + 8 * D_WAVES + 4; i += blockDim.x) vmask[i] = 0u;  // vmask, stat, flag
-  if (tid < 3) ubound[tid] = tid < 2 ? 0x7f800000u : 0u;  // +inf, +inf, queue 0
-  if (tid == 3) {
-    // hints: the grid pairs that won the previous fit of these series (a.best still holds it: only
-    // this block -- or, split, the second arriver of its two halves -- rewrites it, at the
-    // end) go first, so the branch and bound starts from a near-optimal bound
-    unsigned hp[2] = {0xffffu, 0xffffu};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int b = (hints && n0 + r < a.N) ? a.best[n0 + r] : -1;
-      const int q = (b >= 0 && b < a.G) ? b / 2 : -1;
-      if (q >= pi_lo && q < pi_hi && (r == 0 || (unsigned)q != hp[0])) hp[r] = (unsigned)q;
-    }
-    ubound[3] = hp[0] | (hp[1] << 16);
-  }
+  d_lds_init(L, a, tid, n0, hints, pi_lo, pi_hi);
   const int head = a.head_dev ? *a.head_dev : a.head;
   __syncthreads();
 
-  // ---- stage: one thread per (series, 8 consecutive phases), all seasons of them in ------
-  // flight at once.  Aligned rings (R, m, ld multiples of 8, 16-B row base): the phase
-  // groups are shifted by phi = (pad - head) mod 8 so that each season's 8 columns are
-  // one aligned 16-byte chunk (one load per season, no per-element address math);
-  // otherwise one clamped 2-byte load per element.
-  {
-    constexpr int GRP = 8;
-    const int R = a.ring_len;
-    const bool al = (R % GRP == 0) && (m % GRP == 0) && (a.ld % GRP == 0) &&
-                    ((((unsigned long long)a.hist) & 15ull) == 0);
-    const int phi = al ? (((a.pad - head) % GRP) + GRP) % GRP : 0;
-    const int ostart = phi ? phi - GRP : 0;
-    const int ngrp = (m - ostart + GRP - 1) / GRP;
-    float s0 = 0.f, c0 = 0.f, s1 = 0.f, c1 = 0.f, s0b = 0.f, c0b = 0.f, s1b = 0.f, c1b = 0.f;
-    int bad = 0;
-    for (int g = tid; g < 2 * ngrp; g += blockDim.x) {
-      const int r = g >= ngrp ? 1 : 0, o0 = ostart + (g - r * ngrp) * GRP;
-      const int n = n0 + r;
-      const bool real = n < a.N;
-      const bf16_t* row = (const bf16_t*)a.hist + (long long)(real ? n : 0) * a.ld;
-      float y[D_MAXSEG][GRP];
-      if (al) {
-#pragma unroll
-        for (int k = 0; k < D_MAXSEG; ++k) {
-          const int t0 = k * m + o0 - a.pad;  // logical index of element 0 (multiple-of-8 column)
-          int c = (head + t0) % R;
-          c += c < 0 ? R : 0;
-          uint4 w = make_uint4(0u, 0u, 0u, 0u);
-          if (k < nseg) w = *(const uint4*)(row + c);  // k < nseg is block-uniform
-          const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-          for (int u = 0; u < GRP; ++u) {
-            const unsigned x = ww[u >> 1];
-            const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
-            const bool ok = real && k < nseg;
-            // the padding series of an odd N is zeros (keeps the pair on the fast path)
-            y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < D_MAXSEG; ++k) {
-#pragma unroll
-          for (int u = 0; u < GRP; ++u) {
-            // branch-free: every load is issued (clamped to a valid column) and the value
-            // selected afterwards, so all of them are in flight before the first wait
-            const bool ok = real && k < nseg && o0 + u < m;
-            const int t = k * m + o0 + u - a.pad;
-            const bool pos = t >= 0;
-            int c = head + ((ok && pos) ? t : 0);
-            c -= (c >= R) ? R : 0;
-            const float v = bf16_to_f32(row[c]);
-            y[k][u] = ok ? (pos ? v : fm_nan()) : 0.f;
-          }
-        }
-      }
-      // (lane, step) of the group's first in-range phase; later phases step from it
-      const int ob = o0 > 0 ? o0 : 0;
-      const int jjb = ob / K, ib = ob - jjb * K;
-      unsigned vlo = 0u, vhi = 0u;  // season-0 validity bits for words o0 >> 5 and (o0 + 7) >> 5
-#pragma unroll
-      for (int u = 0; u < GRP; ++u) {
-        const int o = o0 + u;
-        if (o >= 0 && o < m) {
-          int i = ib + (o - ob), jj = jjb;
-          if (i >= K) { i -= K; ++jj; }
-          const bool v0 = y[0][u] == y[0][u];
-          float* blk = dl + (size_t)r * ns1 * SEA + dl_off(i, jj);
-          blk[0] = v0 ? y[1][u] - y[0][u] : y[1][u];  // + l0 for valid y0 once the means are known
-          if (v0) {
-            if ((o >> 5) == ((o0 < 0 ? 0 : o0) >> 5)) vlo |= 1u << (o & 31);
-            else vhi |= 1u << (o & 31);
-          }
-#pragma unroll
-          for (int k = 1; k < D_MAXSEG - 1; ++k)
-            if (k < ns1) blk[(size_t)k * SEA] = y[k + 1][u] - y[k][u];
-#pragma unroll
-          for (int k = 1; k < D_MAXSEG; ++k)
-            if (k < nseg && y[k][u] != y[k][u]) bad = 1;
-          if (o < HALF_HB) {
-            float yl = y[1][u];
-#pragma unroll
-            for (int k = 2; k < D_MAXSEG; ++k)
-              if (k == ns1) yl = y[k][u];
-            ylast[r * HALF_HB + o] = yl;
-          }
-          const bool v1 = y[1][u] == y[1][u];
-          const float y0v = v0 ? y[0][u] : 0.f, y0c = v0 ? 1.f : 0.f;
-          const float y1v = v1 ? y[1][u] : 0.f, y1c = v1 ? 1.f : 0.f;
-          if (r == 0) { s0 += y0v; c0 += y0c; s1 += y1v; c1 += y1c; }
-          else { s0b += y0v; c0b += y0c; s1b += y1v; c1b += y1c; }
-        }
-      }
-      const int wlo = (o0 < 0 ? 0 : o0) >> 5;
-      if (vlo) atomicOr(&vmask[r * NMW + wlo], vlo);
-      if (vhi) atomicOr(&vmask[r * NMW + wlo + 1], vhi);
-    }
-    s0 = wave_sum(s0); c0 = wave_sum(c0); s1 = wave_sum(s1); c1 = wave_sum(c1);
-    s0b = wave_sum(s0b); c0b = wave_sum(c0b); s1b = wave_sum(s1b); c1b = wave_sum(c1b);
-    // per-wave slots summed in wave order below: a float atomicAdd's order would make l0 / b0
-    // (and a beta = 0 fit's trend) differ in the last bit from run to run
-    if (lane == 0) {
-      float* sw = stat + 8 * w;
-      sw[0] = s0; sw[1] = c0; sw[2] = s1; sw[3] = c1;
-      sw[4] = s0b; sw[5] = c0b; sw[6] = s1b; sw[7] = c1b;
-    }
-    if (bad) atomicOr(flag, 1);
-  }
+  int bad = 0;
+  d_stage(L, a, n0, head, tid, lane, w, bad);
+  if (bad) atomicOr(L.flag, 1);
   __syncthreads();
-  if (*flag) {  // block-uniform: a gap past season 0 — the gapped kernel takes the pair
+  if (*L.flag) {  // block-uniform: a gap past season 0 — the gapped kernel takes the pair
     if (tid == 0 && hid == 0) {
       const int q = atomicAdd(deferred, 1);
       if (q < (a.N + 1) / 2) deferred[1 + q] = n0;  // a stale count can never write past the pair list
@@ -1326,33 +1586,14 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
     return;
   }
   float l0r[2], b0r[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    float st[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int v = 0; v < D_WAVES; ++v)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) st[u] += stat[8 * v + 4 * r + u];
-    l0r[r] = st[1] > 0.f ? st[0] / st[1] : 0.f;
-    b0r[r] = ((st[3] > 0.f ? st[2] / st[3] : 0.f) - l0r[r]) / (float)m;
-  }
-  // D^(1) = y1 - s0 with s0 = y0 - l0 where y0 is valid (0 elsewhere)
-  for (int col = tid; col < 2 * m; col += blockDim.x) {
-    const int r = col >= m ? 1 : 0, o = col - r * m;
-    if ((vmask[r * NMW + (o >> 5)] >> (o & 31)) & 1u) {
-      const int jj = o / K, i = o - jj * K;
-      dl[(size_t)r * ns1 * SEA + dl_off(i, jj)] += l0r[r];
-    }
-  }
+  d_means(L, m, ns1, tid, l0r, b0r);
   __syncthreads();
 
-  const float l0 = half ? l0r[1] : l0r[0], b0 = half ? b0r[1] : b0r[0];
-  const float* mydl = dl + (size_t)half * ns1 * SEA + j * 4;
+  const float l0 = pick(l0r, half), b0 = pick(b0r, half);
+  const float* mydl = L.dl + (size_t)half * ns1 * SEA + j * 4;
   const int last_addr = ((lane & 32) | 31) << 2;  // bpermute source: lane 31 / 63
-  float bestSSE = __builtin_huge_valf();
-  int bestIdx = 0x7fffffff;
-  float bestL = l0, bestB = b0;
-  float* mybest = bests + (w * 2 + half) * HALF_HB;
+  Best best = {__builtin_huge_valf(), 0x7fffffff, l0, b0};
+  float* mybest = L.bests + (w * 2 + half) * HALF_HB;
   const int nwaves = blockDim.x / FM_WAVE;
   // Exact branch and bound over the grid (PRUNE): ubound[half] is the smallest
   // complete SSE any wave of this block has found for that series.  A per-lane SSE only
@@ -1363,96 +1604,53 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
   // Queue order: the hint pairs (previous winners), then the rest in grid order.
   const int npb = pi_hi - pi_lo;
   // the hint pairs are fixed for the block: read once (an LDS round trip per pair otherwise)
-  const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)ubound[3]);
+  const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)L.ubound[L.HINTS]);
   for (int k = w; k < npb;) {
-    const int pi = hint_pair_at(k, pi_lo, hints_pp);
-    const int c0 = 2 * pi;
-    const int c1i = (2 * pi + 1 < a.G) ? 2 * pi + 1 : c0;
-    const cfp tab = const_ptr(a.pair_tab + (size_t)pi * TS);
-    const v2f c1 = ldv2(tab), c2 = ldv2(tab + 2), g1a = ldv2(tab + 4);
-    const cfp W = tab + PairTab<K>::W0;
-    const cfp tb = tab + PairTab<K>::B0;
-    const v2f one = splat2(1.f), zero = splat2(0.f);
-    Mat2 Bj;  // B^(lane & 15)
-    Mat2 Bp[4];  // B^1, B^2, B^4, B^8 of the next scan
-    Bj.a = one; Bj.b = zero; Bj.c = zero; Bj.d = one;
-#pragma unroll
-    for (int bit = 0; bit < 4; ++bit) Bp[bit] = ldmat(tb + 8 * bit);
-    fence_sched();  // all four requested before the first is used: one scalar-cache wait, not four
-#pragma unroll
-    for (int bit = 0; bit < 4; ++bit) {
-      const Mat2 r = matmul(Bj, Bp[bit]);
-      if ((lane >> bit) & 1) Bj = r;
-    }
+    GridPair<K> gp(a, hint_pair_at(k, pi_lo, hints_pp), lane);
     v2f D[K];
-    v2f X1 = splat2(l0 + b0), X2 = splat2(b0), sse = zero;  // (f, b) at the season start
+    v2f X1 = splat2(l0 + b0), X2 = splat2(b0), sse = splat2(0.f);  // (f, b) at the season start
     v2f p1, p2;
-    d_pass1<K>(mydl, W, D, p1, p2);
+    d_pass1<K>(mydl, gp.W, D, p1, p2);
     int alive = 1;  // per lane: 0 once this lane's partial SSEs exceed the bound (read wave-wide)
     for (int sg = 1; sg < nseg - 1; ++sg) {
       v2f x1, x2;
       Chunk8f c0;
       v2f w0[16];
-      d_chunk0<K>(mydl + (size_t)sg * SEA, launder(W), c0, w0);  // in flight during the scan
-      half_uniform_scan_pre(Bp, launder(tb), p1, p2, X1, X2, Bj, odd_row, x1, x2);
-      d_pass2<K, true>(mydl + (size_t)sg * SEA, D, c1, c2, g1a, launder(W), x1, x2, sse, p1, p2, tb, Bp,
-                       PRUNE, ubound + half, &alive, &c0, w0);
+      d_chunk0<K>(mydl + (size_t)sg * SEA, launder(gp.W), c0, w0);  // in flight during the scan
+      half_uniform_scan_pre(gp.Bp, launder(gp.tb), p1, p2, X1, X2, gp.Bj, odd_row, x1, x2);
+      d_pass2<K, true>(mydl + (size_t)sg * SEA, D, gp.c1, gp.c2, gp.g1a, launder(gp.W), x1, x2, sse, p1, p2, gp.tb,
+                       gp.Bp, PRUNE, L.ubound + half, &alive, &c0, w0);
       X1 = half_last_bp(x1, last_addr);
       X2 = half_last_bp(x2, last_addr);
       if (PRUNE && !__any(alive)) break;
     }
     if (!PRUNE || __any(alive)) {
       v2f x1, x2, d1, d2;
-      half_uniform_scan_pre(Bp, tb, p1, p2, X1, X2, Bj, odd_row, x1, x2);
-      d_pass2<K, false>(mydl, D, c1, c2, g1a, W, x1, x2, sse, d1, d2);
+      half_uniform_scan_pre(gp.Bp, gp.tb, p1, p2, X1, X2, gp.Bj, odd_row, x1, x2);
+      d_pass2<K, false>(mydl, D, gp.c1, gp.c2, gp.g1a, gp.W, x1, x2, sse, d1, d2);
       X1 = half_last_bp(x1, last_addr);
       X2 = half_last_bp(x2, last_addr);
       sse = half_sum_last(sse);
       sse = half_last_bp(sse, last_addr);  // lane 31 / 63 -> the whole half
-      const bool upd0 = (sse.x < bestSSE || (sse.x == bestSSE && c0 < bestIdx));
-      if (upd0) { bestSSE = sse.x; bestIdx = c0; bestL = X1.x - X2.x; bestB = X2.x; }
-      const bool upd1 = (c1i != c0) && (sse.y < bestSSE || (sse.y == bestSSE && c1i < bestIdx));
-      if (upd1) { bestSSE = sse.y; bestIdx = c1i; bestL = X1.y - X2.y; bestB = X2.y; }
-      if (j == 0 && (upd0 || upd1)) {
-        const float* yl = ylast + half * HALF_HB;
-#pragma unroll
-        for (int i = 0; i < K && i < HALF_HB; ++i)
-          if (i < hmax) mybest[i] = yl[i] - (upd1 ? D[i].y : D[i].x);
-      }
-      // publish the bound (SSE >= 0: float order is unsigned-int order; a NaN never lowers it)
-      if (PRUNE && j == 0 && (upd0 || upd1))
-        __hip_atomic_fetch_min(ubound + half, __float_as_uint(bestSSE), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_WORKGROUP);
+      take_candidate<PRUNE>(best, sse, X1, X2, gp.c0, gp.c1i, j == 0, L.ubound + half,
+                            [&](bool upd1) __attribute__((always_inline)) {
+        first_lane_phases<K>(mybest, L.ylast + half * HALF_HB, D, upd1, j, hmax);
+      });
     }
-    // next pair: the first round is static (pi_lo + w), later ones come from the queue
-    int q = 0;
-    if (lane == 0)
-      q = __hip_atomic_fetch_add(ubound + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    k = nwaves + __builtin_amdgcn_readfirstlane(q);
+    k = queue_pop(L.ubound + L.QUEUE, lane, nwaves);
   }
 
   // ---- arg-min across the 4 waves; wave r finishes series n0 + r ----------------------
-  if (j == 0) {
-    float* wb = wbest + (w * 2 + half) * 4;
-    wb[0] = bestSSE;
-    wb[1] = __int_as_float(bestIdx);
-    wb[2] = bestL;
-    wb[3] = bestB;
-  }
+  if (j == 0) put_wave_best<2>(L.wbest, w, half, best);
   __syncthreads();
   if (w >= 2) return;
   const int r = w, n = n0 + r;
   if (n >= a.N) return;
-  int win = 0;
-  for (int q = 1; q < nwaves; ++q) {
-    const float sq = wbest[(q * 2 + r) * 4], sw = wbest[(win * 2 + r) * 4];
-    const int iq = __float_as_int(wbest[(q * 2 + r) * 4 + 1]), iw = __float_as_int(wbest[(win * 2 + r) * 4 + 1]);
-    if (sq < sw || (sq == sw && iq < iw)) win = q;
-  }
-  const float* wb = wbest + (win * 2 + r) * 4;
+  const int win = wave_argmin<2>(L.wbest, r, nwaves);
+  const float* wb = L.wbest + (win * 2 + r) * 4;
   float gSSE = wb[0], gL = wb[2], gB = wb[3];
   int gIdx = __float_as_int(wb[1]);
-  float* sb = bests + (win * 2 + r) * HALF_HB;
+  float* sb = L.bests + (win * 2 + r) * HALF_HB;
   if (slot >= 0) {
     // publish this half's best: system-scope (sc0 sc1) stores, which write through every
     // cache level, drained before the device-scope arrival count; the second arriver reads
@@ -1486,23 +1684,8 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
   }
-  const float nvr = (float)(ns1 * m);  // fast path: every sample past season 0 is valid
-  const float sig = sqrtf(gSSE / fmaxf(nvr, 1.f));
-  if (lane == 0) {
-    a.level[n] = gL;
-    a.trend[n] = gB;
-    a.sigma[n] = sig;
-    a.best[n] = gIdx;
-  }
-  const int Tp = a.Tp;
-  if (a.season_hb && lane < hmax) a.season_hb[(long long)n * HALF_HB + lane] = sb[lane];
-  if (a.nvalid_out && lane == 0) a.nvalid_out[n] = nvr;
-  detect_epilogue_wave(a.det, n, sig, nvr, [&](int h) {
-    int ph = (Tp - 1 + h) % m;
-    if (ph < 0) ph += m;
-    ph = ph < HALF_HB ? ph : HALF_HB - 1;  // host guarantees ph < hmax; clamp keeps LDS reads in bounds
-    return gL + (float)h * gB + sb[ph];
-  }, gIdx);
+  // fast path: every sample past season 0 is valid
+  finish_series(a, n, lane, hmax, gSSE, gIdx, gL, gB, sb, (float)(ns1 * m));
 }
 
 // Workgroups [0, n_full) fit whole series pairs 0..n_full-1; the rest are split-tail
@@ -1535,24 +1718,12 @@ __global__ __launch_bounds__(256, 2) void hw_d_kernel(const SmoothArgs a, int hm
 constexpr int Q_S = 4;  // series per wave / workgroup
 template <int K, bool PRUNE>
 __device__ __forceinline__ void hw_q_block(const SmoothArgs& a, int hmax, int n0, int* deferred, int hints) {
-  constexpr int SEA = DLay<K>::SEASON;
-  constexpr int TS = PairTab<K>::SIZE;
-  constexpr int M = 16 * K;
-  constexpr int NMW = (M + 31) / 32;
+  using Lds = DLds<K, Q_S>;
+  constexpr int SEA = Lds::SEA;
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
   const int sid = lane >> 4, j = lane & 15;
   const int nseg = a.Tp / a.seg, m = a.m, ns1 = nseg - 1;
-
-  // ---- LDS: dl[4][ns1][SEA] | vmask[4][NMW] | stat[4 waves][4][4] | flag | ylast[4][HB] | bests[4][4][HB]
-  //          | wbest[4][4][4] | ubound[4] | queue | hints
-  float* dl = (float*)fm_hw_smem;
-  unsigned* vmask = (unsigned*)(dl + (size_t)Q_S * ns1 * SEA);
-  float* stat = (float*)(vmask + Q_S * NMW);
-  int* flag = (int*)(stat + 4 * Q_S * D_WAVES);
-  float* ylast = (float*)(flag + 4);
-  float* bests = ylast + Q_S * HALF_HB;
-  float* wbest = bests + 4 * Q_S * HALF_HB;
-  unsigned* ubound = (unsigned*)(wbest + 4 * Q_S * 4);  // [0..3] bounds, [4] queue, [5] hints
+  const Lds L(ns1);
 
   const int P = (a.N + 1) / 2;
   int* gflags = deferred + 4 + P;
@@ -1570,128 +1741,24 @@ __device__ __forceinline__ void hw_q_block(const SmoothArgs& a, int hmax, int n0
     defer();
     return;
   }
-  for (int i = tid; i < Q_S * NMW + 4 * Q_S * D_WAVES + 4; i += blockDim.x) vmask[i] = 0u;  // vmask, stat, flag
-  if (tid < Q_S + 1) ubound[tid] = tid < Q_S ? 0x7f800000u : 0u;  // +inf per series, queue 0
-  if (tid == Q_S + 1) {
-    unsigned hp[2] = {0xffffu, 0xffffu};
-    const int npairs = (a.G + 1) / 2;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int b = (hints && n0 + r < a.N) ? a.best[n0 + r] : -1;
-      const int q = (b >= 0 && b < a.G) ? b / 2 : -1;
-      if (q >= 0 && q < npairs && (r == 0 || (unsigned)q != hp[0])) hp[r] = (unsigned)q;
-    }
-    ubound[Q_S + 1] = hp[0] | (hp[1] << 16);
-  }
+  const int npb = (a.G + 1) / 2;
+  d_lds_init(L, a, tid, n0, hints, 0, npb);
   const int head = a.head_dev ? *a.head_dev : a.head;
   __syncthreads();
 
-  // ---- stage: one thread per (series, 8 consecutive phases), all seasons of them in flight
-  {
-    constexpr int GRP = 8;
-    const int R = a.ring_len;
-    const bool al = (R % GRP == 0) && (m % GRP == 0) && (a.ld % GRP == 0) &&
-                    ((((unsigned long long)a.hist) & 15ull) == 0);
-    const int phi = al ? (((a.pad - head) % GRP) + GRP) % GRP : 0;
-    const int ostart = phi ? phi - GRP : 0;
-    const int ngrp = (m - ostart + GRP - 1) / GRP;
-    float acc[Q_S][4];
-#pragma unroll
-    for (int r = 0; r < Q_S; ++r)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc[r][u] = 0.f;
-    int bad = 0;
-    for (int g = tid; g < Q_S * ngrp; g += blockDim.x) {
-      const int r = g / ngrp, o0 = ostart + (g - r * ngrp) * GRP;
-      const int n = n0 + r;
-      const bool real = n < a.N;
-      const bf16_t* row = (const bf16_t*)a.hist + (long long)(real ? n : 0) * a.ld;
-      float y[D_MAXSEG][GRP];
-      if (al) {
-#pragma unroll
-        for (int k = 0; k < D_MAXSEG; ++k) {
-          const int t0 = k * m + o0 - a.pad;
-          int c = (head + t0) % R;
-          c += c < 0 ? R : 0;
-          uint4 wv = make_uint4(0u, 0u, 0u, 0u);
-          if (k < nseg) wv = *(const uint4*)(row + c);
-          const unsigned ww[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-          for (int u = 0; u < GRP; ++u) {
-            const unsigned x = ww[u >> 1];
-            const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
-            const bool ok = real && k < nseg;
-            y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < D_MAXSEG; ++k) {
-#pragma unroll
-          for (int u = 0; u < GRP; ++u) {
-            const bool ok = real && k < nseg && o0 + u < m;
-            const int t = k * m + o0 + u - a.pad;
-            const bool pos = t >= 0;
-            int c = head + ((ok && pos) ? t : 0);
-            c -= (c >= R) ? R : 0;
-            const float v = bf16_to_f32(row[c]);
-            y[k][u] = ok ? (pos ? v : fm_nan()) : 0.f;
-          }
-        }
-      }
-      float s0 = 0.f, c0 = 0.f, s1 = 0.f, c1 = 0.f;
-#pragma unroll
-      for (int u = 0; u < GRP; ++u) {
-        const int o = o0 + u;
-        if (o >= 0 && o < m) {
-          const int jj = o / K, i = o - jj * K;
-          const bool v0 = y[0][u] == y[0][u];
-          float* blk = dl + (size_t)r * ns1 * SEA + dl_off(i, jj);
-          blk[0] = v0 ? y[1][u] - y[0][u] : y[1][u];  // + l0 for valid y0 once the means are known
-          if (v0) atomicOr(&vmask[r * NMW + (o >> 5)], 1u << (o & 31));
-#pragma unroll
-          for (int k = 1; k < D_MAXSEG - 1; ++k)
-            if (k < ns1) blk[(size_t)k * SEA] = y[k + 1][u] - y[k][u];
-#pragma unroll
-          for (int k = 1; k < D_MAXSEG; ++k)
-            if (k < nseg && y[k][u] != y[k][u]) bad = 1;
-          if (o < HALF_HB) {
-            float yl = y[1][u];
-#pragma unroll
-            for (int k = 2; k < D_MAXSEG; ++k)
-              if (k == ns1) yl = y[k][u];
-            ylast[r * HALF_HB + o] = yl;
-          }
-          const bool v1 = y[1][u] == y[1][u];
-          s0 += v0 ? y[0][u] : 0.f;
-          c0 += v0 ? 1.f : 0.f;
-          s1 += v1 ? y[1][u] : 0.f;
-          c1 += v1 ? 1.f : 0.f;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < Q_S; ++q)
-        if (q == r) { acc[q][0] += s0; acc[q][1] += c0; acc[q][2] += s1; acc[q][3] += c1; }
-    }
-    // per-wave slots summed in wave order below (deterministic, see hw_d_block)
-#pragma unroll
-    for (int q = 0; q < Q_S; ++q)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc[q][u] = wave_sum(acc[q][u]);
-    if (lane == 0) {
-      float* sw = stat + 4 * Q_S * w;
-#pragma unroll
-      for (int q = 0; q < Q_S; ++q)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) sw[4 * q + u] = acc[q][u];
-    }
-    if (bad) atomicOr(flag, 1);
-  }
+  int bad = 0;
+  d_stage(L, a, n0, head, tid, lane, w, bad);
+  if (bad) atomicOr(L.flag, 1);
   __syncthreads();
-  if (*flag) {  // block-uniform: a gap past season 0 — the 32-lane gapped kernel takes both pairs
+  if (*L.flag) {  // block-uniform: a gap past season 0 — the 32-lane gapped kernel takes both pairs
     defer();
     return;
   }
+  // The quad block's own copy of d_means (plain arrays and loops; same values): with d_means
+  // here the compiler contracts some a * b + c * d of the walk the other way round
+  // (-ffp-contract=fast picks the product to fuse by use counts, which depend on the code
+  // around it) and sigma moves by 2 - 3 ulp on a few series.
+  constexpr int NMW = Lds::NMW;
   float l0r[Q_S], b0r[Q_S];
 #pragma unroll
   for (int r = 0; r < Q_S; ++r) {
@@ -1699,134 +1766,72 @@ __device__ __forceinline__ void hw_q_block(const SmoothArgs& a, int hmax, int n0
 #pragma unroll
     for (int v = 0; v < D_WAVES; ++v)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) st[u] += stat[4 * Q_S * v + 4 * r + u];
+      for (int u = 0; u < 4; ++u) st[u] += L.stat[4 * Q_S * v + 4 * r + u];
     l0r[r] = st[1] > 0.f ? st[0] / st[1] : 0.f;
     b0r[r] = ((st[3] > 0.f ? st[2] / st[3] : 0.f) - l0r[r]) / (float)m;
   }
   for (int col = tid; col < Q_S * m; col += blockDim.x) {
     const int r = col / m, o = col - r * m;
-    if ((vmask[r * NMW + (o >> 5)] >> (o & 31)) & 1u) {
+    if ((L.vmask[r * NMW + (o >> 5)] >> (o & 31)) & 1u) {
       const int jj = o / K, i = o - jj * K;
-      dl[(size_t)r * ns1 * SEA + dl_off(i, jj)] += l0r[r];
+      L.dl[(size_t)r * ns1 * SEA + dl_off(i, jj)] += l0r[r];
     }
   }
   __syncthreads();
 
-  const float l0 = sid == 0 ? l0r[0] : sid == 1 ? l0r[1] : sid == 2 ? l0r[2] : l0r[3];
-  const float b0 = sid == 0 ? b0r[0] : sid == 1 ? b0r[1] : sid == 2 ? b0r[2] : b0r[3];
-  const float* mydl = dl + (size_t)sid * ns1 * SEA + j * 4;
+  const float l0 = pick(l0r, sid), b0 = pick(b0r, sid);
+  const float* mydl = L.dl + (size_t)sid * ns1 * SEA + j * 4;
   const int last_addr = ((lane & 48) | 15) << 2;  // bpermute source: lane 15 of the row
-  float bestSSE = __builtin_huge_valf();
-  int bestIdx = 0x7fffffff;
-  float bestL = l0, bestB = b0;
-  float* mybest = bests + (w * Q_S + sid) * HALF_HB;
+  Best best = {__builtin_huge_valf(), 0x7fffffff, l0, b0};
+  float* mybest = L.bests + (w * Q_S + sid) * HALF_HB;
   const int nwaves = blockDim.x / FM_WAVE;
-  const int npb = (a.G + 1) / 2;
-  const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)ubound[Q_S + 1]);
+  const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)L.ubound[L.HINTS]);
   for (int k = w; k < npb;) {
-    const int pi = hint_pair_at(k, 0, hints_pp);
-    const int c0 = 2 * pi;
-    const int c1i = (2 * pi + 1 < a.G) ? 2 * pi + 1 : c0;
-    const cfp tab = const_ptr(a.pair_tab + (size_t)pi * TS);
-    const v2f c1 = ldv2(tab), c2 = ldv2(tab + 2), g1a = ldv2(tab + 4);
-    const cfp W = tab + PairTab<K>::W0;
-    const cfp tb = tab + PairTab<K>::B0;
-    const v2f one = splat2(1.f), zero = splat2(0.f);
-    Mat2 Bj;
-    Mat2 Bp[4];
-    Bj.a = one; Bj.b = zero; Bj.c = zero; Bj.d = one;
-#pragma unroll
-    for (int bit = 0; bit < 4; ++bit) Bp[bit] = ldmat(tb + 8 * bit);
-    fence_sched();
-#pragma unroll
-    for (int bit = 0; bit < 4; ++bit) {
-      const Mat2 r = matmul(Bj, Bp[bit]);
-      if ((lane >> bit) & 1) Bj = r;
-    }
+    GridPair<K> gp(a, hint_pair_at(k, 0, hints_pp), lane);
     v2f D[K];
-    v2f X1 = splat2(l0 + b0), X2 = splat2(b0), sse = zero;
+    v2f X1 = splat2(l0 + b0), X2 = splat2(b0), sse = splat2(0.f);
     v2f p1, p2;
-    d_pass1<K>(mydl, W, D, p1, p2);
+    d_pass1<K>(mydl, gp.W, D, p1, p2);
     int alive = 1;
     for (int sg = 1; sg < nseg - 1; ++sg) {
       v2f x1, x2;
       Chunk8f c0;
       v2f w0[16];
-      d_chunk0<K>(mydl + (size_t)sg * SEA, launder(W), c0, w0);
-      row_uniform_scan_pre(Bp, p1, p2, X1, X2, Bj, x1, x2);
-      d_pass2<K, true, false, false, 16>(mydl + (size_t)sg * SEA, D, c1, c2, g1a, launder(W), x1, x2, sse, p1, p2,
-                                         tb, Bp, PRUNE, ubound + sid, &alive, &c0, w0);
+      d_chunk0<K>(mydl + (size_t)sg * SEA, launder(gp.W), c0, w0);
+      row_uniform_scan_pre(gp.Bp, p1, p2, X1, X2, gp.Bj, x1, x2);
+      d_pass2<K, true, false, false, 16>(mydl + (size_t)sg * SEA, D, gp.c1, gp.c2, gp.g1a, launder(gp.W), x1, x2, sse,
+                                         p1, p2, gp.tb, gp.Bp, PRUNE, L.ubound + sid, &alive, &c0, w0);
       X1 = half_last_bp(x1, last_addr);
       X2 = half_last_bp(x2, last_addr);
       if (PRUNE && !__any(alive)) break;
     }
     if (!PRUNE || __any(alive)) {
       v2f x1, x2, d1, d2;
-      row_uniform_scan_pre(Bp, p1, p2, X1, X2, Bj, x1, x2);
-      d_pass2<K, false, false, false, 16>(mydl, D, c1, c2, g1a, W, x1, x2, sse, d1, d2);
+      row_uniform_scan_pre(gp.Bp, p1, p2, X1, X2, gp.Bj, x1, x2);
+      d_pass2<K, false, false, false, 16>(mydl, D, gp.c1, gp.c2, gp.g1a, gp.W, x1, x2, sse, d1, d2);
       X1 = half_last_bp(x1, last_addr);
       X2 = half_last_bp(x2, last_addr);
       sse = row_sum_last(sse);
       sse = half_last_bp(sse, last_addr);  // lane 15 of the row -> the whole row
-      const bool upd0 = (sse.x < bestSSE || (sse.x == bestSSE && c0 < bestIdx));
-      if (upd0) { bestSSE = sse.x; bestIdx = c0; bestL = X1.x - X2.x; bestB = X2.x; }
-      const bool upd1 = (c1i != c0) && (sse.y < bestSSE || (sse.y == bestSSE && c1i < bestIdx));
-      if (upd1) { bestSSE = sse.y; bestIdx = c1i; bestL = X1.y - X2.y; bestB = X2.y; }
-      if (j == 0 && (upd0 || upd1)) {
-        const float* yl = ylast + sid * HALF_HB;
-#pragma unroll
-        for (int i = 0; i < K && i < HALF_HB; ++i)
-          if (i < hmax) mybest[i] = yl[i] - (upd1 ? D[i].y : D[i].x);
-      }
-      if (PRUNE && j == 0 && (upd0 || upd1))
-        __hip_atomic_fetch_min(ubound + sid, __float_as_uint(bestSSE), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_WORKGROUP);
+      take_candidate<PRUNE>(best, sse, X1, X2, gp.c0, gp.c1i, j == 0, L.ubound + sid,
+                            [&](bool upd1) __attribute__((always_inline)) {
+        first_lane_phases<K>(mybest, L.ylast + sid * HALF_HB, D, upd1, j, hmax);
+      });
     }
-    int q = 0;
-    if (lane == 0)
-      q = __hip_atomic_fetch_add(ubound + Q_S, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    k = nwaves + __builtin_amdgcn_readfirstlane(q);
+    k = queue_pop(L.ubound + L.QUEUE, lane, nwaves);
   }
 
   // ---- arg-min across the 4 waves; wave r finishes series n0 + r ----------------------
-  if (j == 0) {
-    float* wb = wbest + (w * Q_S + sid) * 4;
-    wb[0] = bestSSE;
-    wb[1] = __int_as_float(bestIdx);
-    wb[2] = bestL;
-    wb[3] = bestB;
-  }
+  if (j == 0) put_wave_best<Q_S>(L.wbest, w, sid, best);
   __syncthreads();
   if (w >= Q_S) return;
   const int r = w, n = n0 + r;
   if (n >= a.N) return;
-  int win = 0;
-  for (int q = 1; q < nwaves; ++q) {
-    const float sq = wbest[(q * Q_S + r) * 4], sw = wbest[(win * Q_S + r) * 4];
-    const int iq = __float_as_int(wbest[(q * Q_S + r) * 4 + 1]), iw = __float_as_int(wbest[(win * Q_S + r) * 4 + 1]);
-    if (sq < sw || (sq == sw && iq < iw)) win = q;
-  }
-  const float* wb = wbest + (win * Q_S + r) * 4;
-  const float gSSE = wb[0], gL = wb[2], gB = wb[3];
-  const int gIdx = __float_as_int(wb[1]);
-  const float* sb = bests + (win * Q_S + r) * HALF_HB;
-  const float nvr = (float)(ns1 * m);  // fast path: every sample past season 0 is valid
-  const float sig = sqrtf(gSSE / fmaxf(nvr, 1.f));
-  if (lane == 0) {
-    a.level[n] = gL;
-    a.trend[n] = gB;
-    a.sigma[n] = sig;
-    a.best[n] = gIdx;
-  }
-  const int Tp = a.Tp;
-  if (a.season_hb && lane < hmax) a.season_hb[(long long)n * HALF_HB + lane] = sb[lane];
-  if (a.nvalid_out && lane == 0) a.nvalid_out[n] = nvr;
-  detect_epilogue_wave(a.det, n, sig, nvr, [&](int h) {
-    int ph = (Tp - 1 + h) % m;
-    if (ph < 0) ph += m;
-    ph = ph < HALF_HB ? ph : HALF_HB - 1;
-    return gL + (float)h * gB + sb[ph];
-  }, gIdx);
+  const int win = wave_argmin<Q_S>(L.wbest, r, nwaves);
+  const float* wb = L.wbest + (win * Q_S + r) * 4;
+  // fast path: every sample past season 0 is valid
+  finish_series(a, n, lane, hmax, wb[0], __float_as_int(wb[1]), wb[2], wb[3], L.bests + (win * Q_S + r) * HALF_HB,
+                (float)(ns1 * m));
 }
 
 template <int K, bool PRUNE>
@@ -1940,9 +1945,8 @@ __device__ __forceinline__ void dg_season(bool m2, bool r1, const float* blk, v2
 
 template <int K, bool PRUNE>
 __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n0, int hints, int* gflags) {
-  constexpr int SEA = DLay<K>::SEASON;
-  constexpr int TS = PairTab<K>::SIZE;
-  constexpr int NMW = (32 * K + 31) / 32;
+  using Lds = DLds<K, 2>;
+  constexpr int SEA = Lds::SEA;
   // thread / lane ids re-derived through an opaque asm per pair: the queue loop of
   // hw_dg_kernel then holds no lane-derived addresses across pairs (they spilled)
   int tid = threadIdx.x, lane = lane_id();
@@ -1952,36 +1956,20 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
   const bool odd_row = ((lane >> 4) & 1) != 0;
   const int nseg = a.Tp / a.seg, m = a.m, ns1 = nseg - 1;
   const int npairs = (a.G + 1) / 2;
+  const Lds L(ns1);
 
-  // ---- LDS: the hw_d_block layout, then mbits[2][ns1][32][2] | segm[2][ns1] | nvc[2]
-  float* dl = (float*)fm_hw_smem;
-  unsigned* vmask = (unsigned*)(dl + (size_t)2 * ns1 * SEA);
-  float* stat = (float*)(vmask + 2 * NMW);
-  int* flag = (int*)(stat + 8 * D_WAVES);
-  float* ylast = (float*)(flag + 4);
-  float* bests = ylast + 2 * HALF_HB;
-  float* wbest = bests + 4 * 2 * HALF_HB;
-  unsigned* ubound = (unsigned*)(wbest + 4 * 2 * 4);
-  unsigned* mbits = ubound + 4;
-  int* segm = (int*)(mbits + 2 * ns1 * 64);
-  float* nvc = (float*)(segm + 2 * ns1);
-
-  for (int i = tid; i < 2 * NMW + 8 * D_WAVES + 4; i += blockDim.x) vmask[i] = 0u;
-  for (int i = tid; i < 2 * ns1 * 64 + 2 * ns1 + 2; i += blockDim.x) mbits[i] = 0u;  // mbits, segm, nvc = 0.f
-  if (tid < 3) ubound[tid] = tid < 2 ? 0x7f800000u : 0u;
-  if (tid == 3) {
-    unsigned hp[2] = {0xffffu, 0xffffu};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int b = (hints && n0 + r < a.N) ? a.best[n0 + r] : -1;
-      const int q = (b >= 0 && b < a.G) ? b / 2 : -1;
-      if (q >= 0 && q < npairs && (r == 0 || (unsigned)q != hp[0])) hp[r] = (unsigned)q;
-    }
-    ubound[3] = hp[0] | (hp[1] << 16);
-  }
+  d_lds_init(L, a, tid, n0, hints, 0, npairs);
+  for (int i = tid; i < (int)Lds::gap_words(ns1); i += blockDim.x) L.mbits[i] = 0u;  // mbits, segm, nvc = 0.f
   const int head = a.head_dev ? *a.head_dev : a.head;
   __syncthreads();
 
+  // From here on the gapped block has its own copy of what the dense blocks share (staging with
+  // the imputation in place of the NaN flag, initial state, pair set-up, candidate update, queue
+  // pop, finish).  hw_dg<45> sits at the 256-register ceiling and hw_dg<9> at 124 of 128: through
+  // the shared staging they took more registers / scratch, sigma moved by a few ulp on some
+  // series (the contraction choice, see hw_q_block) and the fit was 0.3 % slower; through the
+  // shared grid-loop pieces and finish the scratch of hw_dg<45> moved (28 -> 20 B per lane).
+  constexpr int NMW = Lds::NMW;
   // ---- stage (as hw_d_block: aligned rings in 16-byte season chunks, else per element) -----
   {
     constexpr int GRP = 8;
@@ -2048,14 +2036,14 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
             if (k < nseg) {
               if (y[k][u] != y[k][u]) {
                 y[k][u] = 0.f;
-                atomicOr(&mbits[((r * ns1 + (k - 1)) * 32 + jj) * 2 + (i >> 5)], 1u << (i & 31));
-                segm[r * ns1 + (k - 1)] = 1;
+                atomicOr(&L.mbits[((r * ns1 + (k - 1)) * 32 + jj) * 2 + (i >> 5)], 1u << (i & 31));
+                L.segm[r * ns1 + (k - 1)] = 1;
               } else {
                 if (r == 0) nv0 += 1.f; else nv1 += 1.f;
               }
             }
           }
-          float* blk = dl + (size_t)r * ns1 * SEA + dl_off(i, jj);
+          float* blk = L.dl + (size_t)r * ns1 * SEA + dl_off(i, jj);
           blk[0] = v0 ? y[1][u] - y[0][u] : y[1][u];  // D^(1) = y1* - s0; + l0 for valid y0 below
           if (v0) {
             if ((o >> 5) == ((o0 < 0 ? 0 : o0) >> 5)) vlo |= 1u << (o & 31);
@@ -2069,7 +2057,7 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
 #pragma unroll
             for (int k = 2; k < D_MAXSEG; ++k)
               if (k == ns1) yl = y[k][u];
-            ylast[r * HALF_HB + o] = yl;
+            L.ylast[r * HALF_HB + o] = yl;
           }
           // season-1 mean: observed points only (the imputed 0s are not data)
           const float y0v = v0 ? y[0][u] : 0.f, y0c = v0 ? 1.f : 0.f;
@@ -2079,18 +2067,18 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
         }
       }
       const int wlo = (o0 < 0 ? 0 : o0) >> 5;
-      if (vlo) atomicOr(&vmask[r * NMW + wlo], vlo);
-      if (vhi) atomicOr(&vmask[r * NMW + wlo + 1], vhi);
+      if (vlo) atomicOr(&L.vmask[r * NMW + wlo], vlo);
+      if (vhi) atomicOr(&L.vmask[r * NMW + wlo + 1], vhi);
     }
     s0 = wave_sum(s0); c0 = wave_sum(c0); s1 = wave_sum(s1); c1 = wave_sum(c1);
     s0b = wave_sum(s0b); c0b = wave_sum(c0b); s1b = wave_sum(s1b); c1b = wave_sum(c1b);
     nv0 = wave_sum(nv0); nv1 = wave_sum(nv1);
     if (lane == 0) {
-      float* sw = stat + 8 * w;
+      float* sw = L.stat + 8 * w;
       sw[0] = s0; sw[1] = c0; sw[2] = s1; sw[3] = c1;
       sw[4] = s0b; sw[5] = c0b; sw[6] = s1b; sw[7] = c1b;
-      atomicAdd(&nvc[0], nv0);  // integer-valued: exact in any order
-      atomicAdd(&nvc[1], nv1);
+      atomicAdd(&L.nvc[0], nv0);  // integer-valued: exact in any order
+      atomicAdd(&L.nvc[1], nv1);
     }
   }
   __syncthreads();
@@ -2101,40 +2089,38 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
 #pragma unroll
     for (int v = 0; v < D_WAVES; ++v)
 #pragma unroll
-      for (int u = 0; u < 4; ++u) st[u] += stat[8 * v + 4 * r + u];
+      for (int u = 0; u < 4; ++u) st[u] += L.stat[8 * v + 4 * r + u];
     l0r[r] = st[1] > 0.f ? st[0] / st[1] : 0.f;
     b0r[r] = ((st[3] > 0.f ? st[2] / st[3] : 0.f) - l0r[r]) / (float)m;
   }
   for (int col = tid; col < 2 * m; col += blockDim.x) {
     const int r = col >= m ? 1 : 0, o = col - r * m;
-    if ((vmask[r * NMW + (o >> 5)] >> (o & 31)) & 1u) {
+    if ((L.vmask[r * NMW + (o >> 5)] >> (o & 31)) & 1u) {
       const int jj = o / K, i = o - jj * K;
-      dl[(size_t)r * ns1 * SEA + dl_off(i, jj)] += l0r[r];
+      L.dl[(size_t)r * ns1 * SEA + dl_off(i, jj)] += l0r[r];
     }
   }
   // gapped seasons of the pair (either series): bit sg for season sg (1 .. ns1)
   int segbits = 0;
-  for (int k = 0; k < ns1; ++k) segbits |= (segm[k] | segm[ns1 + k]) ? (2 << k) : 0;
+  for (int k = 0; k < ns1; ++k) segbits |= (L.segm[k] | L.segm[ns1 + k]) ? (2 << k) : 0;
   segbits = __builtin_amdgcn_readfirstlane(segbits);
   if (segbits == 0 && tid == 0) gflags[n0 >> 1] = 0;  // gap-free now: hw_d_kernel stages it next time
   __syncthreads();
 
-  const float l0 = half ? l0r[1] : l0r[0], b0 = half ? b0r[1] : b0r[0];
-  const float* mydl = dl + (size_t)half * ns1 * SEA + j * 4;
-  const unsigned* mymb = mbits + ((size_t)half * ns1 * 32 + j) * 2;  // + (sg - 1) * 64
+  const float l0 = pick(l0r, half), b0 = pick(b0r, half);
+  const float* mydl = L.dl + (size_t)half * ns1 * SEA + j * 4;
+  const unsigned* mymb = L.mbits + ((size_t)half * ns1 * 32 + j) * 2;  // + (sg - 1) * 64
   const int last_addr = ((lane & 32) | 31) << 2;
-  float bestSSE = __builtin_huge_valf();
-  int bestIdx = 0x7fffffff;
-  float bestL = l0, bestB = b0;
-  float* mybest = bests + (w * 2 + half) * HALF_HB;
+  Best best = {__builtin_huge_valf(), 0x7fffffff, l0, b0};
+  float* mybest = L.bests + (w * 2 + half) * HALF_HB;
   const int nwaves = blockDim.x / FM_WAVE;
-  const float* powbase = a.pair_tab + (size_t)npairs * TS;  // [npairs][K + 1][8]: A^0 .. A^K
-  const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)ubound[3]);
+  const float* powbase = a.pair_tab + (size_t)npairs * PairTab<K>::SIZE;  // [npairs][K + 1][8]: A^0 .. A^K
+  const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)L.ubound[L.HINTS]);
   for (int k = w; k < npairs;) {
     const int pi = hint_pair_at(k, 0, hints_pp);
     const int c0 = 2 * pi;
     const int c1i = (2 * pi + 1 < a.G) ? 2 * pi + 1 : c0;
-    const cfp tab = const_ptr(a.pair_tab + (size_t)pi * TS);
+    const cfp tab = const_ptr(a.pair_tab + (size_t)pi * PairTab<K>::SIZE);
     const v2f c1 = ldv2(tab), c2 = ldv2(tab + 2), g1a = ldv2(tab + 4);
     const cfp W = tab + PairTab<K>::W0;
     const cfp tb = tab + PairTab<K>::B0;
@@ -2178,8 +2164,8 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
       const unsigned* mb2 = mymb + (size_t)(sg - 1) * 64;
       const unsigned* mb1 = mb2 + 64;
       const unsigned n2lo = mb2[0], n2hi = mb2[1], n1lo = mb1[0], n1hi = mb1[1];
-      dg_season<K>(m2, r1, mydl + (size_t)sg * SEA, D, c1, c2, g1a, launder(W), x1, x2, sse, p1, p2, tb, Bp,
-                   PRUNE, ubound + half, &alive, ~n2lo, ~n2hi, ~n1lo, ~n1hi);
+      dg_season<K>(m2, r1, mydl + (size_t)sg * SEA, D, c1, c2, g1a, launder(W), x1, x2, sse, p1, p2, tb,
+                   Bp, PRUNE, L.ubound + half, &alive, ~n2lo, ~n2hi, ~n1lo, ~n1hi);
       // the gapped variant ran pass 1 as the recurrence (whichever of its masks it needed):
       // the next scan takes the general lane maps
       general = m2 || r1;
@@ -2202,8 +2188,8 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
       }
       if ((segbits >> ns1) & 1) {
         const unsigned* mb2 = mymb + (size_t)(ns1 - 1) * 64;
-        d_pass2<K, false, true, false>(mydl, D, c1, c2, g1a, W, x1, x2, sse, d1, d2, nullptr, nullptr, false,
-                                       nullptr, nullptr, nullptr, nullptr, ~mb2[0], ~mb2[1]);
+        d_pass2<K, false, true, false>(mydl, D, c1, c2, g1a, W, x1, x2, sse, d1, d2, nullptr, nullptr,
+                                       false, nullptr, nullptr, nullptr, nullptr, ~mb2[0], ~mb2[1]);
       } else {
         d_pass2<K, false>(mydl, D, c1, c2, g1a, W, x1, x2, sse, d1, d2);
       }
@@ -2211,15 +2197,15 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
       X2 = half_last_bp(x2, last_addr);
       sse = half_sum_last(sse);
       sse = half_last_bp(sse, last_addr);
-      const bool upd0 = (sse.x < bestSSE || (sse.x == bestSSE && c0 < bestIdx));
-      if (upd0) { bestSSE = sse.x; bestIdx = c0; bestL = X1.x - X2.x; bestB = X2.x; }
-      const bool upd1 = (c1i != c0) && (sse.y < bestSSE || (sse.y == bestSSE && c1i < bestIdx));
-      if (upd1) { bestSSE = sse.y; bestIdx = c1i; bestL = X1.y - X2.y; bestB = X2.y; }
       // the forecast's seasonal phases 0 .. hmax - 1 from the lanes that own them: lane 0 alone
       // while hmax <= K; at K = 9 (the gapped pairs of the 300 s step's quad path, which takes
       // horizons up to 16) phases 9 .. 15 are lane 1's
+      const bool upd0 = (sse.x < best.sse || (sse.x == best.sse && c0 < best.idx));
+      if (upd0) { best.sse = sse.x; best.idx = c0; best.L = X1.x - X2.x; best.B = X2.x; }
+      const bool upd1 = (c1i != c0) && (sse.y < best.sse || (sse.y == best.sse && c1i < best.idx));
+      if (upd1) { best.sse = sse.y; best.idx = c1i; best.L = X1.y - X2.y; best.B = X2.y; }
       if ((upd0 || upd1) && j * K < hmax) {
-        const float* yl = ylast + half * HALF_HB;
+        const float* yl = L.ylast + half * HALF_HB;
 #pragma unroll
         for (int i = 0; i < K && i < HALF_HB; ++i) {
           const int ph = j * K + i;
@@ -2227,22 +2213,22 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
         }
       }
       if (PRUNE && j == 0 && (upd0 || upd1))
-        __hip_atomic_fetch_min(ubound + half, __float_as_uint(bestSSE), __ATOMIC_RELAXED,
+        __hip_atomic_fetch_min(L.ubound + half, __float_as_uint(best.sse), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     int q = 0;
     if (lane == 0)
-      q = __hip_atomic_fetch_add(ubound + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      q = __hip_atomic_fetch_add(L.ubound + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     k = nwaves + __builtin_amdgcn_readfirstlane(q);
   }
 
   // ---- arg-min across the 4 waves; wave r finishes series n0 + r ----------------------
   if (j == 0) {
-    float* wb = wbest + (w * 2 + half) * 4;
-    wb[0] = bestSSE;
-    wb[1] = __int_as_float(bestIdx);
-    wb[2] = bestL;
-    wb[3] = bestB;
+    float* wb = L.wbest + (w * 2 + half) * 4;
+    wb[0] = best.sse;
+    wb[1] = __int_as_float(best.idx);
+    wb[2] = best.L;
+    wb[3] = best.B;
   }
   __syncthreads();
   if (w >= 2) return;
@@ -2250,15 +2236,15 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
   if (n >= a.N) return;
   int win = 0;
   for (int q = 1; q < nwaves; ++q) {
-    const float sq = wbest[(q * 2 + r) * 4], sw = wbest[(win * 2 + r) * 4];
-    const int iq = __float_as_int(wbest[(q * 2 + r) * 4 + 1]), iw = __float_as_int(wbest[(win * 2 + r) * 4 + 1]);
+    const float sq = L.wbest[(q * 2 + r) * 4], sw = L.wbest[(win * 2 + r) * 4];
+    const int iq = __float_as_int(L.wbest[(q * 2 + r) * 4 + 1]), iw = __float_as_int(L.wbest[(win * 2 + r) * 4 + 1]);
     if (sq < sw || (sq == sw && iq < iw)) win = q;
   }
-  const float* wb = wbest + (win * 2 + r) * 4;
+  const float* wb = L.wbest + (win * 2 + r) * 4;
   const float gSSE = wb[0], gL = wb[2], gB = wb[3];
   const int gIdx = __float_as_int(wb[1]);
-  const float* sb = bests + (win * 2 + r) * HALF_HB;
-  const float nvr = nvc[r];
+  const float* sb = L.bests + (win * 2 + r) * HALF_HB;
+  const float nvr = L.nvc[r];
   const float sig = sqrtf(gSSE / fmaxf(nvr, 1.f));
   if (lane == 0) {
     a.level[n] = gL;
@@ -2316,8 +2302,6 @@ __global__ __launch_bounds__(256, 2) void hw_dg_kernel(const SmoothArgs a, int h
   }
 }
 
-extern "C" size_t fm_hw_dg_lds_bytes(int Tp, int seg, int K);
-
 // A/B instrument (FOREMAST_HW_DG_ALL=1): every pair is listed for the gapped kernel, so its
 // cost on gap-free seasons can be timed against hw_d_kernel's on the same data
 __global__ void hw_dg_list_all_kernel(int* deferred, int pairs) {
@@ -2328,30 +2312,70 @@ __global__ void hw_dg_list_all_kernel(int* deferred, int pairs) {
 // the seasons variant 5 is instantiated for: m = 32 K, K steps per lane
 // (1440 = 32 x 45: the 60 s step; 288 = 32 x 9: the 300 s step)
 static bool d_supported_k(int K) { return K == 45 || K == 9; }
+// hw_q_kernel: seasons m = 16 K (K = 18: the 300 s step)
+static bool q_supported_k(int K) { return K == 18; }
 
-extern "C" size_t fm_hw_d_lds_bytes(int Tp, int seg, int K) {
+// LDS bytes of one workgroup, from the layout the kernels carve (DLds); (size_t)-1 where
+// the kernel does not exist
+static size_t d_lds_words(int Tp, int seg, int K, bool gapped) {
   if (!d_supported_k(K) || seg <= 0) return (size_t)-1;
   const int nseg = Tp / seg;
   if (nseg < 2 || nseg > D_MAXSEG) return (size_t)-1;
-  const int NMW = (32 * K + 31) / 32;
-  const int season = D_CHUNK * ((K + 7) / 8);  // DLay<K>::SEASON
-  return ((size_t)2 * (nseg - 1) * season + 2 * NMW + 8 * D_WAVES + 4 + 2 * HALF_HB + 4 * 2 * HALF_HB + 4 * 2 * 4 +
-          4) * 4;
+  const int ns1 = nseg - 1;
+  const size_t gap = gapped ? DLds<45, 2>::gap_words(ns1) : 0;  // the extension does not depend on K
+  return (K == 45 ? DLds<45, 2>::words(ns1) : DLds<9, 2>::words(ns1)) + gap;
 }
 
-// hw_dg_block: the hw_d_block layout + per-(series, season, lane) 64-bit miss masks, per
-// (series, season) gap flags and the two valid-point counts
-// hw_q_kernel: seasons m = 16 K (K = 18: the 300 s step)
-static bool q_supported_k(int K) { return K == 18; }
+extern "C" size_t fm_hw_d_lds_bytes(int Tp, int seg, int K) {
+  const size_t words = d_lds_words(Tp, seg, K, false);
+  return words == (size_t)-1 ? words : words * 4;
+}
+
+extern "C" size_t fm_hw_dg_lds_bytes(int Tp, int seg, int K) {
+  const size_t words = d_lds_words(Tp, seg, K, true);
+  return words == (size_t)-1 ? words : words * 4;
+}
 
 extern "C" size_t fm_hw_q_lds_bytes(int Tp, int seg, int K) {
   if (!q_supported_k(K) || seg != 16 * K) return (size_t)-1;
   const int nseg = Tp / seg;
   if (nseg < 2 || nseg > D_MAXSEG) return (size_t)-1;
-  const int NMW = (16 * K + 31) / 32;
-  const int season = D_CHUNK * ((K + 7) / 8);
-  return ((size_t)Q_S * (nseg - 1) * season + Q_S * NMW + 4 * Q_S * D_WAVES + 4 + Q_S * HALF_HB +
-          4 * Q_S * HALF_HB + 4 * Q_S * 4 + 8) * 4;
+  return DLds<18, Q_S>::words(nseg - 1) * 4;
+}
+
+// FOREMAST_HW_PRUNE=0 turns the exact grid branch and bound off (A/B runs);
+// FOREMAST_HW_HINTS=0 walks the grid in order instead of the previous winners first
+// (hints only matter to the branch and bound)
+struct GridSwitches {
+  bool prune;
+  int hints;
+};
+static GridSwitches grid_switches() {
+  const char* pe = getenv("FOREMAST_HW_PRUNE");
+  const char* he = getenv("FOREMAST_HW_HINTS");
+  GridSwitches s;
+  s.prune = !(pe && pe[0] == '0');
+  s.hints = (s.prune && !(he && he[0] == '0')) ? 1 : 0;
+  return s;
+}
+
+template <bool PRUNE>
+static hipError_t launch_q_fit(const SmoothArgs* a, const float* tab_g, int hmax, int* deferred, int hints,
+                               hipStream_t st) {
+  const int K = a->K;
+  const size_t lds = fm_hw_q_lds_bytes(a->Tp, a->seg, K);
+  const size_t dlds = fm_hw_dg_lds_bytes(a->Tp, a->seg, K / 2);
+  const int quads = (a->N + 3) / 4;
+  hipLaunchKernelGGL((hw_q_kernel<18, PRUNE>), dim3(quads), dim3(256), lds, st, *a, hmax, deferred, hints);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  SmoothArgs ag = *a;
+  ag.pair_tab = tab_g;
+  ag.K = K / 2;
+  const int pairs = (a->N + 1) / 2;
+  const int grid = pairs < 512 ? pairs : 512;
+  hipLaunchKernelGGL((hw_dg_kernel<9, PRUNE>), dim3(grid), dim3(256), dlds, st, ag, hmax, deferred, hints);
+  return hipGetLastError();
 }
 
 // Variant 5 at m = 16 K: hw_q_kernel over quads, then the gapped kernel at K / 2 (32 lanes x
@@ -2364,38 +2388,12 @@ extern "C" int fm_hw_q_fit(const SmoothArgs* a, const float* tab_g, int hmax, in
       hmax > HALF_HB)
     return (int)hipErrorNotSupported;
   if (a->N <= 0) return 0;
-  const size_t lds = fm_hw_q_lds_bytes(a->Tp, a->seg, K);
-  const size_t dlds = fm_hw_dg_lds_bytes(a->Tp, a->seg, K / 2);
-  if (lds > 80 * 1024 || dlds > 80 * 1024) return (int)hipErrorNotSupported;
+  if (fm_hw_q_lds_bytes(a->Tp, a->seg, K) > 80 * 1024 || fm_hw_dg_lds_bytes(a->Tp, a->seg, K / 2) > 80 * 1024)
+    return (int)hipErrorNotSupported;
   if (!deferred) return (int)hipErrorInvalidValue;
-  const char* pe = getenv("FOREMAST_HW_PRUNE");
-  const bool prune = !(pe && pe[0] == '0');
-  const char* he = getenv("FOREMAST_HW_HINTS");
-  const int hints = (prune && !(he && he[0] == '0')) ? 1 : 0;
-  const int quads = (a->N + 3) / 4;
-  if (prune)
-    hipLaunchKernelGGL((hw_q_kernel<18, true>), dim3(quads), dim3(256), lds, st, *a, hmax, deferred, hints);
-  else
-    hipLaunchKernelGGL((hw_q_kernel<18, false>), dim3(quads), dim3(256), lds, st, *a, hmax, deferred, hints);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  SmoothArgs ag = *a;
-  ag.pair_tab = tab_g;
-  ag.K = K / 2;
-  const int pairs = (a->N + 1) / 2;
-  const int grid = pairs < 512 ? pairs : 512;
-  if (prune)
-    hipLaunchKernelGGL((hw_dg_kernel<9, true>), dim3(grid), dim3(256), dlds, st, ag, hmax, deferred, hints);
-  else
-    hipLaunchKernelGGL((hw_dg_kernel<9, false>), dim3(grid), dim3(256), dlds, st, ag, hmax, deferred, hints);
-  return (int)hipGetLastError();
-}
-
-extern "C" size_t fm_hw_dg_lds_bytes(int Tp, int seg, int K) {
-  const size_t base = fm_hw_d_lds_bytes(Tp, seg, K);
-  if (base == (size_t)-1) return base;
-  const int ns1 = Tp / seg - 1;
-  return base + ((size_t)2 * ns1 * 64 + 2 * ns1 + 2) * 4;
+  const GridSwitches sw = grid_switches();
+  return (int)(sw.prune ? launch_q_fit<true>(a, tab_g, hmax, deferred, sw.hints, st)
+                        : launch_q_fit<false>(a, tab_g, hmax, deferred, sw.hints, st));
 }
 
 // Deferred detection for HW variants 4/5: band, verdict, per-app counters and the K9
@@ -2479,37 +2477,9 @@ extern "C" int fm_hw_d_split_plan(int pairs, int slots, int max_split) {
   return best;
 }
 
-// Variant 5 launcher: same contract as fm_hw_half_fit (deferred pairs go to the
-// variant-4 general kernel), at most D_MAXSEG seasons.  `split_ws` (optional):
-// int32 [2 * max_split] arrival counters followed by float [max_split * 2 * 2 *
-// CAND_FLOATS] candidates; the counters must be zero on entry (they are left zero).
-extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
-                                 int slots, hipStream_t st);
-extern "C" int fm_hw_d_fit(const SmoothArgs* a, int hmax, int* deferred, hipStream_t st) {
-  return fm_hw_d_fit_split(a, hmax, deferred, nullptr, 0, 0, st);
-}
-
-template <int K>
+template <int K, bool PRUNE>
 static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split, int slots,
-                               hipStream_t st);
-
-extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
-                                 int slots, hipStream_t st) {
-  const int K = a->K;
-  if (!d_supported_k(K) || a->seg != 32 * K || a->m != a->seg || a->Tp % a->seg != 0 || a->Tp / a->seg < 2 ||
-      a->Tp / a->seg > D_MAXSEG || !a->pair_tab || a->season_out || hmax < 1 || hmax > K || hmax > HALF_HB)
-    return (int)hipErrorNotSupported;
-  if (a->N <= 0) return 0;
-  if (fm_hw_d_lds_bytes(a->Tp, a->seg, K) > 80 * 1024 || fm_hw_dg_lds_bytes(a->Tp, a->seg, K) > 80 * 1024)
-    return (int)hipErrorNotSupported;
-  if (!deferred) return (int)hipErrorInvalidValue;
-  return (int)(K == 45 ? launch_d_fit<45>(a, hmax, deferred, split_ws, max_split, slots, st)
-                       : launch_d_fit<9>(a, hmax, deferred, split_ws, max_split, slots, st));
-}
-
-template <int K>
-static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split, int slots,
-                               hipStream_t st) {
+                               int hints, hipStream_t st) {
   const size_t lds = fm_hw_d_lds_bytes(a->Tp, a->seg, K);
   const int pairs = (a->N + 1) / 2;
   const int S = (split_ws && max_split > 0 && a->G >= 2) ? fm_hw_d_split_plan(pairs, slots, max_split) : 0;
@@ -2517,19 +2487,11 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
   // of each (slot, row) resets its counter
   int* cnt = split_ws;
   float* cand = split_ws ? (float*)(split_ws + 2 * max_split) : nullptr;
-  // FOREMAST_HW_PRUNE=0 turns the exact grid branch and bound off (A/B runs)
-  const char* pe = getenv("FOREMAST_HW_PRUNE");
-  const bool prune = !(pe && pe[0] == '0');
-  const char* he = getenv("FOREMAST_HW_HINTS");  // previous winners first (=0: grid order)
-  const int hints = (prune && !(he && he[0] == '0')) ? 1 : 0;
   const char* da = getenv("FOREMAST_HW_DG_ALL");
   if (da && da[0] == '1')
     hipLaunchKernelGGL(hw_dg_list_all_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, deferred, pairs);
-  else if (prune)
-    hipLaunchKernelGGL((hw_d_kernel<K, true>), dim3(pairs - S + 2 * S), dim3(256), lds, st, *a, hmax, deferred,
-                       pairs - S, cnt, cand, hints);
   else
-    hipLaunchKernelGGL((hw_d_kernel<K, false>), dim3(pairs - S + 2 * S), dim3(256), lds, st, *a, hmax, deferred,
+    hipLaunchKernelGGL((hw_d_kernel<K, PRUNE>), dim3(pairs - S + 2 * S), dim3(256), lds, st, *a, hmax, deferred,
                        pairs - S, cnt, cand, hints);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -2547,11 +2509,33 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
   int grid = pairs < 512 ? pairs : 512;
   const char* gg = getenv("FOREMAST_HW_DG_GRID");  // A/B: workgroups of the gapped kernel
   if (gg && atoi(gg) > 0) grid = atoi(gg) < pairs ? atoi(gg) : pairs;
-  if (prune)
-    hipLaunchKernelGGL((hw_dg_kernel<K, true>), dim3(grid), dim3(256), dlds, st, *a, hmax, deferred, hints);
-  else
-    hipLaunchKernelGGL((hw_dg_kernel<K, false>), dim3(grid), dim3(256), dlds, st, *a, hmax, deferred, hints);
+  hipLaunchKernelGGL((hw_dg_kernel<K, PRUNE>), dim3(grid), dim3(256), dlds, st, *a, hmax, deferred, hints);
   return hipGetLastError();
+}
+
+// Variant 5 launcher: same contract as fm_hw_half_fit, at most D_MAXSEG seasons; deferred
+// pairs go to the variant-5 gapped kernel (hw_dg_kernel), which runs the same residual walk
+// with masked seasons.  `split_ws` (optional): int32 [2 * max_split] arrival counters
+// followed by float [max_split * 2 * 2 * CAND_FLOATS] candidates; the counters must be zero
+// on entry (they are left zero).
+extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
+                                 int slots, hipStream_t st) {
+  const int K = a->K;
+  if (!d_supported_k(K) || a->seg != 32 * K || a->m != a->seg || a->Tp % a->seg != 0 || a->Tp / a->seg < 2 ||
+      a->Tp / a->seg > D_MAXSEG || !a->pair_tab || a->season_out || hmax < 1 || hmax > K || hmax > HALF_HB)
+    return (int)hipErrorNotSupported;
+  if (a->N <= 0) return 0;
+  if (fm_hw_d_lds_bytes(a->Tp, a->seg, K) > 80 * 1024 || fm_hw_dg_lds_bytes(a->Tp, a->seg, K) > 80 * 1024)
+    return (int)hipErrorNotSupported;
+  if (!deferred) return (int)hipErrorInvalidValue;
+  const GridSwitches sw = grid_switches();
+  const auto launch = K == 45 ? (sw.prune ? launch_d_fit<45, true> : launch_d_fit<45, false>)
+                              : (sw.prune ? launch_d_fit<9, true> : launch_d_fit<9, false>);
+  return (int)launch(a, hmax, deferred, split_ws, max_split, slots, sw.hints, st);
+}
+
+extern "C" int fm_hw_d_fit(const SmoothArgs* a, int hmax, int* deferred, hipStream_t st) {
+  return fm_hw_d_fit_split(a, hmax, deferred, nullptr, 0, 0, st);
 }
 
 template <int K, int MODE, typename TIN, int NC, int MINW, bool TAB = false>

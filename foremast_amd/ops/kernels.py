@@ -352,6 +352,43 @@ def smoothing_supported(mode: int, T: int, m: int, bf16: bool) -> bool:
     return lib.fm_smooth_lds_bytes(Tp, m if mode == MODE_HW else 1, seg, int(bf16)) <= LDS_LIMIT
 
 
+def _fit_outputs(out: Optional[Dict[str, torch.Tensor]], N: int, dev, names, m: int = 0,
+                 zeroed=()) -> Dict[str, torch.Tensor]:
+    """Allocate the outputs of a smoothing fit that ``out`` does not hold yet, by name:
+    ``best`` int32 [N], ``season_hb`` [N, HALF_HB], ``season`` [N, m], anything else
+    float32 [N] (``zeroed``: names allocated zero-filled)."""
+    out = {} if out is None else out
+    for name in names:
+        if name not in out:
+            shape = (N, HALF_HB) if name == "season_hb" else (N, m) if name == "season" else (N,)
+            make = torch.zeros if name in zeroed else torch.empty
+            out[name] = make(shape, dtype=torch.int32 if name == "best" else torch.float32, device=dev)
+    return out
+
+
+def _smooth_args(out: Dict[str, torch.Tensor], N: int, *, Tp: int, m: int, pad: int = 0, K: int = 0, seg: int = 0,
+                 hist: Optional[torch.Tensor] = None, head: int = 0, length: int = 0,
+                 grid: Optional[torch.Tensor] = None) -> "nat.SmoothArgs":
+    """The SmoothArgs every smoothing launcher shares: the ring, the geometry, the grid and
+    the level / trend / sigma / best pointers.  What only some launchers use (pair_tab,
+    head_dev, season_out, season_hb / nvalid_out, det) is left to the caller."""
+    a = nat.SmoothArgs()
+    if hist is not None:
+        a.hist = nat.ptr(hist)
+        a.ld = hist.stride(0)
+        a.ring_len = hist.shape[1]
+        a.head = int(head)
+        a.T = int(length)
+    a.Tp, a.pad, a.m, a.K, a.seg = int(Tp), int(pad), int(m), int(K), int(seg)
+    if grid is not None:
+        a.grid = nat.ptr(grid)
+        a.G = grid.shape[0]
+    a.N = N
+    a.level, a.trend, a.sigma = nat.ptr(out["level"]), nat.ptr(out["trend"]), nat.ptr(out["sigma"])
+    a.best = nat.ptr(out.get("best"))
+    return a
+
+
 def smoothing_fit(hist: torch.Tensor, head: int, length: int, mode: int, m: int,
                   grid: torch.Tensor, det: DetectSpec, K: Optional[int] = None,
                   want_season: bool = False, out: Optional[Dict[str, torch.Tensor]] = None,
@@ -422,34 +459,10 @@ def smoothing_fit(hist: torch.Tensor, head: int, length: int, mode: int, m: int,
             k = (mm + 63) // 64
         lds = lib.fm_smooth_lds_bytes(Tp, mm, seg, int(bf16))
         _need(lds <= LDS_LIMIT, f"series too long for LDS staging ({lds} bytes)")
-    out = {} if out is None else out
-    f32 = dict(dtype=torch.float32, device=dev)
-    for kname in ("level", "trend", "sigma"):
-        if kname not in out:
-            out[kname] = torch.empty(N, **f32)
-    if "best" not in out:
-        out["best"] = torch.empty(N, dtype=torch.int32, device=dev)
-    if want_season and mode == MODE_HW and "season" not in out:
-        out["season"] = torch.empty((N, mm), **f32)
-    a = nat.SmoothArgs()
-    a.hist = nat.ptr(hist)
-    a.ld = hist.stride(0)
-    a.ring_len = hist.shape[1]
-    a.head = int(head)
-    a.T = int(length)
-    a.Tp = Tp
-    a.pad = pad
-    a.m = mm
-    a.K = k
-    a.seg = seg
-    a.grid = nat.ptr(grid)
-    a.G = G
-    a.N = N
-    a.level = nat.ptr(out["level"])
-    a.trend = nat.ptr(out["trend"])
-    a.sigma = nat.ptr(out["sigma"])
-    a.best = nat.ptr(out["best"])
-    a.season_out = nat.ptr(out.get("season")) if (want_season and mode == MODE_HW) else 0
+    season = want_season and mode == MODE_HW
+    out = _fit_outputs(out, N, dev, ("level", "trend", "sigma", "best") + (("season",) if season else ()), m=mm)
+    a = _smooth_args(out, N, Tp=Tp, m=mm, pad=pad, K=k, seg=seg, hist=hist, head=head, length=length, grid=grid)
+    a.season_out = nat.ptr(out["season"]) if season else 0
     a.pair_tab = nat.ptr(pair_table(grid, k)) if variant == 3 else 0
     _fill_detect(a.det, det, N, dev, out)
     _set_hvar(a.det, det, grid, mode, mm)
@@ -542,32 +555,8 @@ def _hw_half_fit(lib, hist, head, length, m, grid, det, Tp, pad, hmax, out, resi
     dev = hist.device
     N = hist.shape[0]
     k = m // 16 if quad else m // 32
-    out = {} if out is None else out
-    f32 = dict(dtype=torch.float32, device=dev)
-    for kname in ("level", "trend", "sigma"):
-        if kname not in out:
-            out[kname] = torch.empty(N, **f32)
-    if "best" not in out:
-        out["best"] = torch.empty(N, dtype=torch.int32, device=dev)
-    a = nat.SmoothArgs()
-    a.hist = nat.ptr(hist)
-    a.ld = hist.stride(0)
-    a.ring_len = hist.shape[1]
-    a.head = int(head)
-    a.T = int(length)
-    a.Tp = Tp
-    a.pad = pad
-    a.m = m
-    a.K = k
-    a.seg = m
-    a.grid = nat.ptr(grid)
-    a.G = grid.shape[0]
-    a.N = N
-    a.level = nat.ptr(out["level"])
-    a.trend = nat.ptr(out["trend"])
-    a.sigma = nat.ptr(out["sigma"])
-    a.best = nat.ptr(out["best"])
-    a.season_out = 0
+    out = _fit_outputs(out, N, dev, ("level", "trend", "sigma", "best") + (("season_hb", "nvalid") if defer else ()))
+    a = _smooth_args(out, N, Tp=Tp, m=m, pad=pad, K=k, seg=m, hist=hist, head=head, length=length, grid=grid)
     a.pair_tab = nat.ptr(pair_table(grid, k))
     if head_dev is not None:
         _need(head_dev.dtype == torch.int32 and head_dev.device == dev and head_dev.numel() >= 1,
@@ -576,9 +565,6 @@ def _hw_half_fit(lib, hist, head, length, m, grid, det, Tp, pad, hmax, out, resi
     _fill_detect(a.det, det, N, dev, out)
     _set_hvar(a.det, det, grid, MODE_HW, m)
     if defer:
-        for kname, shape in (("season_hb", (N, HALF_HB)), ("nvalid", (N,))):
-            if kname not in out:
-                out[kname] = torch.empty(shape, **f32)
         a.season_hb = nat.ptr(out["season_hb"])
         a.nvalid_out = nat.ptr(out["nvalid"])
         a.det.C = 0  # no epilogue in the fit
@@ -620,35 +606,11 @@ def _hw_seq_fit(lib, hist, head, length, m, grid, det, Tp, pad, out, want_season
     verdict epilogue is fm_hw_detect_params (inline, or deferred like variants 4 / 5)."""
     dev = hist.device
     N = hist.shape[0]
-    out = {} if out is None else out
-    f32 = dict(dtype=torch.float32, device=dev)
-    for kname in ("level", "trend", "sigma", "nvalid"):
-        if kname not in out:
-            out[kname] = torch.empty(N, **f32)
-    if "best" not in out:
-        out["best"] = torch.empty(N, dtype=torch.int32, device=dev)
-    if "season_hb" not in out:
-        out["season_hb"] = torch.empty((N, HALF_HB), **f32)
-    if want_season and "season" not in out:
-        out["season"] = torch.empty((N, m), **f32)
+    out = _fit_outputs(out, N, dev, ("level", "trend", "sigma", "nvalid", "best", "season_hb")
+                       + (("season",) if want_season else ()), m=m)
     if not defer and detect_after is not None:
         torch.cuda.current_stream(dev).wait_stream(detect_after)  # the inline epilogue reads det.differs
-    a = nat.SmoothArgs()
-    a.hist = nat.ptr(hist)
-    a.ld = hist.stride(0)
-    a.ring_len = hist.shape[1]
-    a.head = int(head)
-    a.T = int(length)
-    a.Tp = int(Tp)
-    a.pad = int(pad)
-    a.m = int(m)
-    a.K = 1
-    a.seg = int(m)
-    a.grid = nat.ptr(grid)
-    a.G = grid.shape[0]
-    a.N = N
-    a.level, a.trend, a.sigma = nat.ptr(out["level"]), nat.ptr(out["trend"]), nat.ptr(out["sigma"])
-    a.best = nat.ptr(out["best"])
+    a = _smooth_args(out, N, Tp=Tp, m=m, pad=pad, K=1, seg=m, hist=hist, head=head, length=length, grid=grid)
     a.season_out = nat.ptr(out["season"]) if want_season else 0
     a.nvalid_out = nat.ptr(out["nvalid"])
     a.season_hb = nat.ptr(out["season_hb"])
@@ -674,30 +636,10 @@ def _es_seq_fit(lib, hist, head, length, mode, grid, det, out, head_dev=None, de
     _need(head_dev is None, "head_dev needs HW variant 4/5 geometry")
     dev = hist.device
     N = hist.shape[0]
-    out = {} if out is None else out
-    f32 = dict(dtype=torch.float32, device=dev)
-    for kname in ("level", "trend", "sigma", "nvalid"):
-        if kname not in out:
-            out[kname] = torch.empty(N, **f32)
-    if "best" not in out:
-        out["best"] = torch.empty(N, dtype=torch.int32, device=dev)
-    if "season_hb" not in out:
-        out["season_hb"] = torch.zeros((N, HALF_HB), **f32)  # ES / DES forecasts carry no seasonal term
-    a = nat.SmoothArgs()
-    a.hist = nat.ptr(hist)
-    a.ld = hist.stride(0)
-    a.ring_len = hist.shape[1]
-    a.head = int(head)
-    a.T = int(length)
-    a.Tp = int(length)
-    a.m = 1
-    a.K = 1
-    a.seg = 1
-    a.grid = nat.ptr(grid)
-    a.G = grid.shape[0]
-    a.N = N
-    a.level, a.trend, a.sigma = nat.ptr(out["level"]), nat.ptr(out["trend"]), nat.ptr(out["sigma"])
-    a.best = nat.ptr(out["best"])
+    # ES / DES forecasts carry no seasonal term: season_hb is zeros
+    out = _fit_outputs(out, N, dev, ("level", "trend", "sigma", "nvalid", "best", "season_hb"),
+                       zeroed=("season_hb",))
+    a = _smooth_args(out, N, Tp=length, m=1, pad=0, K=1, seg=1, hist=hist, head=head, length=length, grid=grid)
     a.nvalid_out = nat.ptr(out["nvalid"])
     a.season_hb = nat.ptr(out["season_hb"])
     _fill_detect(a.det, det, N, dev, out)
@@ -721,11 +663,8 @@ def hw_detect_deferred(out: Dict[str, torch.Tensor], det: DetectSpec, Tp: int, m
         _need(kname in out, f"deferred detection needs out[{kname!r}] from the fit")
     dev = out["level"].device
     N = out["level"].shape[0]
-    a = nat.SmoothArgs()
-    a.N, a.Tp, a.m = N, int(Tp), int(m)
-    a.level, a.trend, a.sigma = nat.ptr(out["level"]), nat.ptr(out["trend"]), nat.ptr(out["sigma"])
+    a = _smooth_args(out, N, Tp=Tp, m=m)  # no ring, no grid: the fit is done
     a.season_hb, a.nvalid_out = nat.ptr(out["season_hb"]), nat.ptr(out["nvalid"])
-    a.best = nat.ptr(out.get("best"))
     _fill_detect(a.det, det, N, dev, out)
     if grid is not None:
         _need("best" in out, "horizon variance needs out['best'] from the fit")

@@ -214,6 +214,67 @@ def test_variant5_at_the_300s_step_matches_reference(K, case, monkeypatch):
     assert torch.equal(d.verdict, out["verdict"].cpu())
 
 
+#            case             m     N  T               R - T  head  outage
+_GEOMETRY = [("elem_pad",     288,  9, 3 * 288 + 100,  97,    61,   False),  # ring not a multiple of 8: per-element staging
+             ("elem_wrap",    288,  9, 3 * 288 + 100,  97,    1000, False),  # the same, the window wraps the ring's end
+             # R = 1072 = 8 x 134: 16-byte chunks, shifted by phi = (188 - 1000) mod 8 = 4, head mid-ring, wrap
+             ("chunk_wrap",   288,  9, 3 * 288 + 100,  108,   1000, False),
+             ("two_seasons",  288,  9, 2 * 288,        0,     0,    False),  # the fused season loop runs zero times
+             ("two_seasons",  1440, 5, 2 * 1440,       0,     0,    False),  # ... in hw_d_block
+             ("elem_outage",  288,  9, 3 * 288 + 100,  97,    61,   True)]   # quads to the K = 9 gapped kernel
+
+
+@pytest.mark.parametrize("case,m,N,T,extra,head,outage", _GEOMETRY, ids=[f"{g[0]}-{g[1]}" for g in _GEOMETRY])
+def test_variant5_staging_geometry_matches_reference(K, case, m, N, T, extra, head, outage, monkeypatch):
+    """The staging shared by the variant-5 kernels at the edges of its geometry: the
+    four-series layout (m = 288; N = 9 is two full quads plus a one-series quad whose second
+    pair does not exist) off the aligned path, with a padded first season and a wrapping
+    ring, the season-count minimum (two seasons: one fitted) on both layouts, and an
+    unaligned ring handing gapped quads to the K = 9 gapped kernel.  Same checks as
+    test_variant5_at_the_300s_step_matches_reference."""
+    dev = torch.device("cuda:0")
+    R = T + extra
+    y = _series(N, T, m, seed=51 + len(case))
+    if outage:
+        y[::3, 2 * m + 17:2 * m + 23] = np.nan            # 30 minutes = 6 points, past season 0
+    ring = torch.tensor(_ring(y, R, head), device=dev).to(torch.bfloat16)
+    # chunked staging needs R, m and the row stride multiples of 8 and a 16-byte base
+    assert (case == "chunk_wrap") <= (R % 8 == 0 and ring.stride(0) % 8 == 0 and ring.data_ptr() % 16 == 0)
+    yl = ring.float().cpu().numpy()[:, (head + np.arange(T)) % R]
+    C = 8
+    hz = torch.tensor([1, 2, 1, 2, 1, 2, 1, 2], dtype=torch.int32)
+    cur = torch.tensor(np.nan_to_num(y[:, -C:], nan=20.0) * 1.05, device=dev)
+    spec = K.DetectSpec(horizons=hz.to(dev), threshold=torch.full((N,), 2.0, device=dev),
+                        bound=torch.full((N,), 3, dtype=torch.int8, device=dev),
+                        min_lower=torch.full((N,), -1e30, device=dev), cur=cur, max_horizon=2)
+    K.hw_clear_gap_flags()
+    before = K.hw_deferred_total(dev)
+    outs = []
+    for prune in ("1", "0"):
+        monkeypatch.setenv("FOREMAST_HW_PRUNE", prune)
+        o = K.smoothing_fit(ring, head, T, sm_ref.MODE_HW, m, GRID.to(dev), spec, variant=5)
+        torch.cuda.synchronize()
+        assert K.last_hw_variant == 5
+        outs.append({k: v.clone() for k, v in o.items()})
+    assert (K.hw_deferred_total(dev) > before) == outage
+    for key in ("best", "level", "trend", "sigma", "verdict", "forecast"):
+        assert torch.equal(outs[0][key], outs[1][key]), key
+    out = outs[0]
+    ref = sm_ref.fit_smoothing(torch.tensor(yl, dtype=torch.float64), sm_ref.MODE_HW, GRID.double(), m=m)
+    kb = out["best"].cpu().long()
+    same = (kb == ref.best).numpy()
+    print(f"{case}-{m}: same {same.mean():.3f} sigma rel err "
+          f"{np.abs(out['sigma'].cpu().numpy() / ref.sigma.numpy() - 1).max():.2e}")
+    assert same.mean() >= 0.75
+    _assert_near_optimal(yl, GRID, sm_ref.MODE_HW, m, kb)
+    np.testing.assert_allclose(out["sigma"].cpu().numpy(), ref.sigma.numpy(), rtol=5e-3)
+    np.testing.assert_allclose(out["level"].cpu().numpy()[same], ref.level.numpy()[same], rtol=2e-3, atol=5e-3)
+    f_ref = sm_ref.forecast(ref, hz.long())
+    np.testing.assert_allclose(out["forecast"].cpu().numpy()[same], f_ref.numpy()[same], rtol=5e-3, atol=2e-2)
+    d = _ref_detect(out, GRID, sm_ref.MODE_HW, m, hz, cur)
+    assert torch.equal(d.verdict, out["verdict"].cpu())
+
+
 @pytest.mark.parametrize("case", ["dense", "outage"])
 def test_quad_kernel_matches_pair_kernel_at_300s(K, case, monkeypatch):
     """At m = 288 variant 5 walks four series per wave (hw_q_kernel, 16 lanes x 18 steps);

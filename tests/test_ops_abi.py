@@ -67,3 +67,38 @@ def test_hw_seq_geometry(lib):
     assert lib.fm_hw_seq_lds_bytes(500, 72, 64) == none       # not a whole number of seasons
     assert lib.fm_hw_seq_lds_bytes(72, 72, 64) == none        # one season: nothing to fit
     assert lib.fm_hw_seq_lds_bytes(2016, 288, 64) == (2 * 4 * (2016 + 4) + 4) * 4  # one grid point per thread
+
+
+def test_hw_variant5_lds_bytes(lib):
+    """Variant 5 (hw_scan.hip hw_d / hw_dg / hw_q kernels): the LDS of one workgroup, from the
+    layout the kernels carve.  Per series and fitted season one fp32 image of 260 floats per
+    8-step chunk; then the fixed blocks (validity mask, per-wave sums, flag, last season's
+    head, per-wave bests, bounds); the gapped kernel adds its miss masks, per-season gap flags
+    and the two valid counts.  2..7 seasons, K = 45 / 9 (32 lanes) and K = 18 (16 lanes)."""
+    nat.load()
+    none = C.c_size_t(-1).value
+
+    def season(K):
+        return 260 * ((K + 7) // 8)
+
+    for K in (45, 9):
+        seg = 32 * K
+        for nseg in range(2, 8):
+            ns1 = nseg - 1
+            d = (2 * ns1 * season(K) + 2 * K + 232) * 4
+            assert lib.fm_hw_d_lds_bytes(nseg * seg, seg, K) == d, (K, nseg)
+            assert lib.fm_hw_dg_lds_bytes(nseg * seg, seg, K) == d + (2 * ns1 * 64 + 2 * ns1 + 2) * 4, (K, nseg)
+        for f in (lib.fm_hw_d_lds_bytes, lib.fm_hw_dg_lds_bytes):
+            assert f(seg, seg, K) == none and f(8 * seg, seg, K) == none       # 1 or 8 seasons
+    K, seg = 18, 288
+    for nseg in range(2, 8):
+        assert lib.fm_hw_q_lds_bytes(nseg * seg, seg, K) == (4 * (nseg - 1) * season(K) + 4 * 9 + 460) * 4, nseg
+    assert lib.fm_hw_q_lds_bytes(seg, seg, K) == none and lib.fm_hw_q_lds_bytes(8 * seg, seg, K) == none
+    assert lib.fm_hw_d_lds_bytes(7 * 1440, 1440, 45) == 76168
+    assert lib.fm_hw_dg_lds_bytes(7 * 1440, 1440, 45) == 79296
+    assert lib.fm_hw_q_lds_bytes(7 * 288, 288, 18) == 76864
+    # unsupported K, and the quad layout off its season (seg != 16 K)
+    for f in (lib.fm_hw_d_lds_bytes, lib.fm_hw_dg_lds_bytes):
+        assert f(7 * 768, 768, 24) == none and f(7 * 576, 576, 18) == none
+    assert lib.fm_hw_q_lds_bytes(7 * 288, 288, 9) == none and lib.fm_hw_q_lds_bytes(7 * 1440, 1440, 45) == none
+    assert lib.fm_hw_q_lds_bytes(7 * 576, 576, 18) == none
