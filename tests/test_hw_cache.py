@@ -2,12 +2,27 @@
 refit and O(1) per-tick state updates, CPU reference vs the gfx950 kernels
 (ops/csrc/hw_state.hip)."""
 
+import importlib.util
+import os
+
+import numpy as np
 import pytest
 import torch
 
 from foremast_amd.brain.engine import ShardSpec, StreamingShard, synthetic_history
 from foremast_amd.models import smoothing as sm
 from foremast_amd.utils.config import BrainConfig
+
+
+def _helper(name):
+    spec = importlib.util.spec_from_file_location(
+        name, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+hc = _helper("hw_state_cases")
 
 
 def _grid():
@@ -48,6 +63,51 @@ def test_hw_update_equals_the_recursion_over_the_extended_series():
     assert st.t_last == ref.t_last
     torch.testing.assert_close(st.level, ref.level)
     torch.testing.assert_close(st.season, ref.season)
+
+
+@pytest.mark.parametrize("name", [c.name for c in hc.CASES])
+def test_hw_run_fp32_matches_the_fp64_oracle(name):
+    """The fp32 reference the engine's CPU path uses (and the GPU tests' yardstick) against
+    the fp64 oracle on every case of helpers/hw_state_cases.py, within 2 x D."""
+    b = hc.build(name)
+    c = b["case"]
+    st = sm.hw_run(torch.from_numpy(b["y"]).float(), b["params"], c.m)
+    assert st.t_last == c.Tp - 1
+    for key, d in (("level", hc.D_LEVEL), ("trend", hc.D_TREND), ("season", hc.D_SEASON)):
+        err = hc.norm_err(getattr(st, key), b["ref"][key], b["unit"])
+        print(f"{name} {key}: fp32 CPU vs fp64 {err.max():.3e} (row {err.argmax()})")
+        assert err.max() <= hc.CPU_HEADROOM * d, (key, err.max(), int(err.argmax()))
+    k = hc.K_ALL
+    assert st.level[k] == 0 and st.trend[k] == 0 and not st.season[k].any() and b["ref"]["nvalid"][k] == 0
+    # the initialisation's edge values, on the oracle itself: an empty season 0 starts the
+    # level at 0, an empty season 1 starts the trend at -l0 / m
+    y0 = np.concatenate([np.full((c.n_rows, c.pad), np.nan), b["y"]], 1)
+    two = hc.oracle_run(y0[:, :2 * c.m], b["params"], c.m, 2 * c.m)
+    l0 = np.nanmean(y0[hc.K_S1, :c.m])
+    assert abs(two["trend"][hc.K_S1] + l0 / c.m) <= 1e-12 * abs(l0) and abs(two["level"][hc.K_S1]) <= 1e-9 * abs(l0)
+
+
+@pytest.mark.parametrize("name,N", [("u130_fp32", 1), ("u130_fp32", 17), ("u130_fp32", 67), ("u130_bf16", 1),
+                                    ("u130_bf16", 17), ("u130_bf16", 67), ("u1440_bf16", 33)])
+def test_hw_update_and_forecast_fp32_match_the_fp64_oracle(name, N):
+    """sm.hw_update from the oracle's state (cast to fp32, as the kernel test starts) and
+    sm.hw_state_forecast at every horizon set of the GPU tests, against the oracle, within 2 x D."""
+    m = hc.CASE_BY_NAME[name].m
+    for npts in (hc.NPTS(m) if m == 130 else (3,)):
+        u = hc.update_inputs(name, N, npts)
+        st = sm.HwState(level=u["start"]["level"].clone(), trend=u["start"]["trend"].clone(),
+                        season=u["start"]["season"].clone(), t_last=u["t_last"], m=m)
+        sm.hw_update(st, torch.from_numpy(u["ynew"]).float(), u["params"])
+        assert st.t_last == u["ref"]["t_last"] == u["t_last"] + npts
+        for key, d in (("level", hc.D_UPD_LEVEL), ("trend", hc.D_UPD_TREND), ("season", hc.D_UPD_SEASON)):
+            err = hc.norm_err(getattr(st, key), u["ref"][key], u["unit"])
+            print(f"{name} N={N} npts={npts} {key}: fp32 CPU vs fp64 {err.max():.3e}")
+            assert err.max() <= hc.CPU_HEADROOM * d, (npts, key, err.max(), int(err.argmax()))
+        for C, per_series in hc.CONFIGS:
+            hz = hc.config_horizons(u, C, per_series)
+            err = hc.norm_err(sm.hw_state_forecast(st, hz.long()), hc.oracle_forecast(u["ref"], hz.numpy()), u["unit"])
+            print(f"{name} N={N} npts={npts} C={C} forecast: fp32 CPU vs fp64 {err.max():.3e}")
+            assert err.max() <= hc.CPU_HEADROOM * hc.D_FORECAST, (npts, C, per_series, err.max())
 
 
 def _shard(dev, refit_every, n=16, R=None, m=48, P=3, W=4, seed=3, dtype=torch.float32):
@@ -111,12 +171,15 @@ def test_hw_state_kernel_matches_reference(dtype, pad):
     grid = _grid()
     best = torch.randint(0, 64, (n,), generator=torch.Generator().manual_seed(4)).int()
     st = K.hw_state(ring, head, T, m, grid.to(dev), best.to(dev))
-    ref = sm.hw_run(yq, grid[best.long()], m)
-    assert st["Tp"] - 1 == ref.t_last
+    ref = hc.oracle_run(yq.double().numpy(), grid[best.long()], m, 5 * m)  # fp64, bounds: 4 x D
+    assert st["Tp"] - 1 == ref["t_last"]
     torch.cuda.synchronize()
-    torch.testing.assert_close(st["level"].cpu(), ref.level, rtol=1e-4, atol=1e-3)
-    torch.testing.assert_close(st["trend"].cpu(), ref.trend, rtol=1e-4, atol=1e-5)
-    torch.testing.assert_close(st["season"].cpu().T, ref.season, rtol=1e-4, atol=1e-3)
+    unit = hc.unit_of(yq.double().numpy())
+    for key in ("level", "trend", "season"):
+        got = st[key].cpu().T if key == "season" else st[key].cpu()
+        err = hc.norm_err(got, ref[key], unit)
+        print(f"{key}: kernel vs fp64 {err.max():.3e}")
+        assert err.max() <= hc.BOUND[key], (key, err.max(), int(err.argmax()))
     nv = (~torch.isnan(torch.cat([torch.full((n, pad), float("nan")), yq], 1)[:, m:])).sum(1).float()
     assert torch.equal(st["nvalid"].cpu(), nv)
 
