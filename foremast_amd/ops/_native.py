@@ -103,7 +103,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.fm_hw_dg_lds_bytes.restype = C.c_size_t
     lib.fm_hw_d_fit.argtypes = [C.POINTER(SmoothArgs), I, P, P]
     lib.fm_hw_d_fit.restype = I
-    lib.fm_hw_d_fit_split.argtypes = [C.POINTER(SmoothArgs), I, P, P, I, I, P]
+    lib.fm_hw_d_fit_split.argtypes = [C.POINTER(SmoothArgs), I, P, P, I, I, P, I]
     lib.fm_hw_d_fit_split.restype = I
     lib.fm_hw_q_lds_bytes.argtypes = [I, I, I]
     lib.fm_hw_q_lds_bytes.restype = C.c_size_t

@@ -1014,15 +1014,25 @@ __device__ __forceinline__ v2f keep_if(v2f e, unsigned keep, int bit) {
 // chunk's word); R1 runs the next season's pass 1 as the masked recurrence from a zero
 // state (p = the lane's end state from zero: its affine offset, exact with gaps) instead
 // of the table sum, whose uniform weights assume every step observed (keep bits k1).
-template <int K, bool FUSE, int R, bool M2 = false, bool R1 = false>
+// SAVE (season 1 of a quad's first pair, hw_d_block): the step's error is kept in E (two
+// steps per register pair) for the sibling pair's replay (d_replay); a compile-time flag: as
+// a nullable run-time pointer it cost registers and scratch on every path.
+template <int K, bool FUSE, int R, bool M2 = false, bool R1 = false, bool SAVE = false>
 __device__ __forceinline__ void d_steps(int q, const Chunk8f& cc, v2f* D, v2f c1, v2f c2, v2f g1a, const v2f* wc,
                                         v2f& x1, v2f& x2, v2f& sse, v2f& p1, v2f& p2, unsigned k2 = 0u,
-                                        unsigned k1 = 0u) {
+                                        unsigned k1 = 0u, v2f* E = nullptr) {
   if constexpr (R < 8) {
     const int i = 8 * q + R;
     if (i < K) {
       v2f e = D[i] - x1;
       if (M2) e = keep_if(e, k2, i & 31);
+      // a 32-bit copy into half of a register pair (steps 2n, 2n + 1 share E[n]): left as a
+      // half of e's own pair, or as 45 single registers that the replay widens to pairs, the
+      // saved errors cost up to twice their registers and the kernel spilled
+      if constexpr (SAVE) {
+        if (i & 1) asm volatile("v_mov_b32 %0, %1" : "=v"(E[i >> 1].y) : "v"(e.x));
+        else asm volatile("v_mov_b32 %0, %1" : "=v"(E[i >> 1].x) : "v"(e.x));
+      }
       const v2f t = x1 + x2;
       x1 = t + c1 * e;
       x2 = x2 + c2 * e;
@@ -1042,7 +1052,7 @@ __device__ __forceinline__ void d_steps(int q, const Chunk8f& cc, v2f* D, v2f c1
         D[i] = D[i] - g1a * e;
       }
     }
-    d_steps<K, FUSE, R + 1, M2, R1>(q, cc, D, c1, c2, g1a, wc, x1, x2, sse, p1, p2, k2, k1);
+    d_steps<K, FUSE, R + 1, M2, R1, SAVE>(q, cc, D, c1, c2, g1a, wc, x1, x2, sse, p1, p2, k2, k1, E);
   }
 }
 
@@ -1061,13 +1071,13 @@ __device__ __forceinline__ void d_chunk0(const float* blk, cfp W, Chunk8f& c, v2
     if (r < 2 * K) w[r] = ldv2(W + 2 * r);
 }
 
-template <int K, bool FUSE, bool M2 = false, bool R1 = false, int L = 32>
+template <int K, bool FUSE, bool M2 = false, bool R1 = false, int L = 32, bool SAVE = false>
 __device__ __forceinline__ void d_pass2(const float* blk, v2f* D, v2f c1, v2f c2, v2f g1a, cfp W, v2f& x1,
                                         v2f& x2, v2f& sse, v2f& p1, v2f& p2, cfp tb = nullptr,
                                         Mat2* Bn = nullptr, bool chk = false, const unsigned* ubp = nullptr,
                                         int* alive = nullptr, const Chunk8f* c0 = nullptr, const v2f* w0 = nullptr,
                                         unsigned k2lo = 0u, unsigned k2hi = 0u, unsigned k1lo = 0u,
-                                        unsigned k1hi = 0u) {
+                                        unsigned k1hi = 0u, v2f* E = nullptr) {
   constexpr int NCH = (K + 7) / 8;
   constexpr bool WTS = FUSE && !R1;  // table pass 1: the chunk's weights
   if (FUSE) { p1 = splat2(0.f); p2 = splat2(0.f); }
@@ -1127,8 +1137,8 @@ __device__ __forceinline__ void d_pass2(const float* blk, v2f* D, v2f c1, v2f c2
     }
     fence_sched();
     // chunk q's steps 8q .. 8q + 7 lie in one 32-bit word of the lane's keep bits
-    d_steps<K, FUSE, 0, M2, R1>(q, cc, D, c1, c2, g1a, wc, x1, x2, sse, p1, p2, q < 4 ? k2lo : k2hi,
-                                q < 4 ? k1lo : k1hi);
+    d_steps<K, FUSE, 0, M2, R1, SAVE>(q, cc, D, c1, c2, g1a, wc, x1, x2, sse, p1, p2, q < 4 ? k2lo : k2hi,
+                                      q < 4 ? k1lo : k1hi, E);
     fence_sched();
   }
   // retire the B prefetch here (it landed during the last chunk) so the wait the compiler
@@ -1150,6 +1160,87 @@ __device__ __forceinline__ int hint_pair_at(int k, int lo, unsigned hp) {
   r += r >= a0 ? 1 : 0;
   r += r >= a1 ? 1 : 0;
   return r;
+}
+
+// ---- hw_d_block's queue when season 1 is shared -------------------------------------------
+// With a grid in quads (rows 4q .. 4q + 3 share alpha and beta: the host's check, see
+// fm_hw_d_fit_split) the grid pairs 2q and 2q + 1 differ in g1a only, and season 1 of every
+// walker starts from the same D^(1): its errors e_i, its (f, b) chain, its SSE and its scan
+// do not depend on gamma.  The queue then hands out items, even [lo, hi) taken as quads:
+//   1. the (at most two, distinct) hint pairs, each alone, as in hint_pair_at (the bound);
+//   2. every quad that holds no hint pair, in grid order: pair 2q walks season 1 and keeps
+//      e_i and the end state, pair 2q + 1 replays it (d_replay);
+//   3. the sibling of each hint pair, alone (none if the hints are each other's siblings):
+//      the smallest granules last, where they even out the end of the block.
+// An item is the pair index, with QUAD_ITEM set for a quad (then the index of its pair 2q).
+constexpr int QUAD_ITEM = 0x10000;
+struct QuadQueue {
+  int h0, h1, nh, nq, n_items;
+  bool sib;
+  __device__ __forceinline__ QuadQueue(int lo, int hi, unsigned hp) {
+    h0 = (int)(hp & 0xffffu);
+    h1 = (int)(hp >> 16);
+    if (h0 == 0xffff) { h0 = h1; h1 = 0xffff; }
+    nh = (h0 != 0xffff) + (h1 != 0xffff);
+    sib = nh == 2 && (h0 ^ 1) == h1;
+    nq = ((hi - lo) >> 1) - (sib ? 1 : nh);  // two distinct hints of one quad are siblings
+    n_items = nh + nq + (sib ? 0 : nh);
+  }
+  __device__ __forceinline__ int at(int k, int lo) const {
+    if (k < nh) return k == 0 ? h0 : h1;
+    k -= nh;
+    if (k < nq) {
+      int r = (lo >> 1) + k;
+      const int q0 = h0 >> 1, q1 = sib ? 0x7fff : h1 >> 1;  // 0xffff >> 1 sorts past every quad
+      const int a0 = q0 < q1 ? q0 : q1, a1 = q0 < q1 ? q1 : q0;
+      r += r >= a0 ? 1 : 0;
+      r += r >= a1 ? 1 : 0;
+      return (2 * r) | QUAD_ITEM;
+    }
+    return (k == nq ? h0 : h1) ^ 1;
+  }
+};
+
+template <int K, int R>
+__device__ __forceinline__ void d_replay_steps(int q, const Chunk8f& cd, const Chunk8f& cy, const v2f* wc,
+                                               const v2f* E, v2f g1a, v2f* D, v2f& p1, v2f& p2) {
+  if constexpr (R < 8) {
+    const int i = 8 * q + R;
+    if (i < K) {
+      D[i] = pk_splat<R & 1>(chunk_pair<R>(cd));
+      D[i] = add_dy<R>(D[i], cy) - g1a * pk_splat<R & 1>(E[i >> 1]);
+      p1 = p1 + wc[2 * R] * D[i];
+      p2 = p2 + wc[2 * R + 1] * D[i];
+    }
+    d_replay_steps<K, R + 1>(q, cd, cy, wc, E, g1a, D, p1, p2);
+  }
+}
+
+// Season 1 of a quad's second pair from the first pair's errors E: D'_i = (D1_i + dy_i) -
+// g1a e_i and season 2's pass 1 over it.  The expressions are those of d_pass1 and d_steps
+// (the same contraction to FMAs), so D, p1, p2 are bit for bit what the pair's own season-1
+// walk leaves; a chunk's weights are requested together as in d_pass1.
+template <int K>
+__device__ __forceinline__ void d_replay(const float* blk, const float* dyb, cfp W, const v2f* E, v2f g1a, v2f* D,
+                                         v2f& p1, v2f& p2) {
+  constexpr int NCH = (K + 7) / 8;
+  p1 = splat2(0.f);
+  p2 = splat2(0.f);
+  Chunk8f cd, cy;
+#pragma unroll
+  for (int q = 0; q < NCH; ++q) {
+    v2f wc[16];
+    W = launder(W);
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (16 * q + r < 2 * K) wc[r] = ldv2(W + 32 * q + 2 * r);
+    // no chunk ahead here: with E live next to D the registers of a second chunk pair spill
+    cd.load(blk + q * D_CHUNK);
+    cy.load(dyb + q * D_CHUNK);
+    fence_sched();
+    d_replay_steps<K, 0>(q, cd, cy, wc, E, g1a, D, p1, p2);
+    fence_sched();
+  }
 }
 
 // ---- variant 5: what hw_d_block, hw_q_block and hw_dg_block share ---------------------------
@@ -1550,7 +1641,8 @@ constexpr int CAND_FLOATS = 4 + HALF_HB;  // SSE, index bits, level, trend, seas
 
 template <int K, bool PRUNE>
 __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0, int* deferred, int pi_lo,
-                                           int pi_hi, int slot, int hid, int* cnt, float* cand, int hints) {
+                                           int pi_hi, int slot, int hid, int* cnt, float* cand, int hints,
+                                           int share) {
   using Lds = DLds<K, 2>;
   constexpr int SEA = Lds::SEA;
   const int tid = threadIdx.x, lane = lane_id(), w = wave_id();
@@ -1605,14 +1697,49 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
   const int npb = pi_hi - pi_lo;
   // the hint pairs are fixed for the block: read once (an LDS round trip per pair otherwise)
   const unsigned hints_pp = (unsigned)__builtin_amdgcn_readfirstlane((int)L.ubound[L.HINTS]);
-  for (int k = w; k < npb;) {
-    GridPair<K> gp(a, hint_pair_at(k, pi_lo, hints_pp), lane);
-    v2f D[K];
-    v2f X1 = splat2(l0 + b0), X2 = splat2(b0), sse = splat2(0.f);  // (f, b) at the season start
-    v2f p1, p2;
-    d_pass1<K>(mydl, gp.W, D, p1, p2);
+  // season 1 shared inside a quad (see QuadQueue): needs a fused season 1 and whole quads
+  const bool quads = share && ns1 >= 2 && ((pi_lo | pi_hi) & 1) == 0;
+  const QuadQueue qq(pi_lo, pi_hi, hints_pp);
+  const int n_items = quads ? qq.n_items : npb;
+  v2f D[K];
+  v2f E[(K + 1) / 2];    // a quad's season-1 errors (two steps per pair), from its first pair to its second
+  float sX1, sX2, ssse;  // and the state after season 1 (both grid points' halves are equal)
+  // One grid pair's walk.  ALONE: all of it, as without sharing.  FIRST (pair 2q of a quad):
+  // season 1 is peeled, saves its errors and its end state, and has no prune check (none
+  // fires this early).  SECOND (pair 2q + 1): season 1 is the replay.  Three instantiations
+  // rather than one loop entered from three places: there the next scan's B matrices were
+  // copied from scalar to vector registers at the end of every season (16 copies, 32
+  // registers), also on the pair queue's path.
+  constexpr int ALONE = 0, FIRST = 1, SECOND = 2;
+  const auto walk = [&](auto mode, int pi) __attribute__((always_inline)) {
+    constexpr int MODE = decltype(mode)::value;
+    GridPair<K> gp(a, pi, lane);
+    v2f X1, X2, sse, p1, p2;
+    if constexpr (MODE == SECOND) {
+      d_replay<K>(mydl, mydl + SEA, gp.W, E, gp.g1a, D, p1, p2);
+      X1 = splat2(sX1); X2 = splat2(sX2); sse = splat2(ssse);
+    } else {
+      X1 = splat2(l0 + b0); X2 = splat2(b0); sse = splat2(0.f);  // (f, b) at the season start
+      d_pass1<K>(mydl, gp.W, D, p1, p2);
+    }
+    if constexpr (MODE == FIRST) {
+      v2f x1, x2;
+      Chunk8f c0;
+      v2f w0[16];
+      // the SSE enters as a value the compiler does not know: told that it is 0, it sums
+      // the first two squares as fma(e0, e0, e1 * e1), not in the season loop's order
+      // fma(e1, e1, e0 * e0), and a sum differs in the last bit
+      asm volatile("" : "+v"(sse));
+      d_chunk0<K>(mydl + SEA, launder(gp.W), c0, w0);
+      half_uniform_scan_pre(gp.Bp, launder(gp.tb), p1, p2, X1, X2, gp.Bj, odd_row, x1, x2);
+      d_pass2<K, true, false, false, 32, true>(mydl + SEA, D, gp.c1, gp.c2, gp.g1a, launder(gp.W), x1, x2, sse, p1, p2,
+                                               gp.tb, gp.Bp, false, nullptr, nullptr, &c0, w0, 0u, 0u, 0u, 0u, E);
+      X1 = half_last_bp(x1, last_addr);
+      X2 = half_last_bp(x2, last_addr);
+      sX1 = X1.x; sX2 = X2.x; ssse = sse.x;
+    }
     int alive = 1;  // per lane: 0 once this lane's partial SSEs exceed the bound (read wave-wide)
-    for (int sg = 1; sg < nseg - 1; ++sg) {
+    for (int sg = MODE == ALONE ? 1 : 2; sg < nseg - 1; ++sg) {
       v2f x1, x2;
       Chunk8f c0;
       v2f w0[16];
@@ -1636,6 +1763,15 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
                             [&](bool upd1) __attribute__((always_inline)) {
         first_lane_phases<K>(mybest, L.ylast + half * HALF_HB, D, upd1, j, hmax);
       });
+    }
+  };
+  for (int k = w; k < n_items;) {
+    const int item = quads ? qq.at(k, pi_lo) : hint_pair_at(k, pi_lo, hints_pp);
+    if (item & QUAD_ITEM) {
+      walk(std::integral_constant<int, FIRST>(), item & 0xffff);
+      walk(std::integral_constant<int, SECOND>(), (item & 0xffff) + 1);
+    } else {
+      walk(std::integral_constant<int, ALONE>(), item);
     }
     k = queue_pop(L.ubound + L.QUEUE, lane, nwaves);
   }
@@ -1692,16 +1828,16 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
 // halves: workgroup n_full + 2 s + h fits half h of the grid of pair n_full + s.
 template <int K, bool PRUNE>
 __global__ __launch_bounds__(256, 2) void hw_d_kernel(const SmoothArgs a, int hmax, int* deferred, int n_full,
-                                                     int* cnt, float* cand, int hints) {
+                                                     int* cnt, float* cand, int hints, int share) {
   const int b = blockIdx.x;
   const int npairs = (a.G + 1) / 2;
   if (b < n_full) {
-    hw_d_block<K, PRUNE>(a, hmax, 2 * b, deferred, 0, npairs, -1, 0, cnt, cand, hints);
+    hw_d_block<K, PRUNE>(a, hmax, 2 * b, deferred, 0, npairs, -1, 0, cnt, cand, hints, share);
     return;
   }
   const int item = b - n_full, slot = item >> 1, h = item & 1, mid = npairs / 2;
   hw_d_block<K, PRUNE>(a, hmax, 2 * (n_full + slot), deferred, h ? mid : 0, h ? npairs : mid, slot, h, cnt, cand,
-                       hints);
+                       hints, share);
 }
 
 
@@ -2345,17 +2481,21 @@ extern "C" size_t fm_hw_q_lds_bytes(int Tp, int seg, int K) {
 
 // FOREMAST_HW_PRUNE=0 turns the exact grid branch and bound off (A/B runs);
 // FOREMAST_HW_HINTS=0 walks the grid in order instead of the previous winners first
-// (hints only matter to the branch and bound)
+// (hints only matter to the branch and bound); FOREMAST_HW_SHARE=0 keeps hw_d_kernel on its
+// pair queue where the grid would allow season 1 to be shared inside a quad (tests, A/B runs)
 struct GridSwitches {
   bool prune;
   int hints;
+  int share;
 };
 static GridSwitches grid_switches() {
   const char* pe = getenv("FOREMAST_HW_PRUNE");
   const char* he = getenv("FOREMAST_HW_HINTS");
+  const char* se = getenv("FOREMAST_HW_SHARE");
   GridSwitches s;
   s.prune = !(pe && pe[0] == '0');
   s.hints = (s.prune && !(he && he[0] == '0')) ? 1 : 0;
+  s.share = !(se && se[0] == '0') ? 1 : 0;
   return s;
 }
 
@@ -2479,7 +2619,7 @@ extern "C" int fm_hw_d_split_plan(int pairs, int slots, int max_split) {
 
 template <int K, bool PRUNE>
 static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split, int slots,
-                               int hints, hipStream_t st) {
+                               int hints, int share, hipStream_t st) {
   const size_t lds = fm_hw_d_lds_bytes(a->Tp, a->seg, K);
   const int pairs = (a->N + 1) / 2;
   const int S = (split_ws && max_split > 0 && a->G >= 2) ? fm_hw_d_split_plan(pairs, slots, max_split) : 0;
@@ -2492,7 +2632,7 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
     hipLaunchKernelGGL(hw_dg_list_all_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, deferred, pairs);
   else
     hipLaunchKernelGGL((hw_d_kernel<K, PRUNE>), dim3(pairs - S + 2 * S), dim3(256), lds, st, *a, hmax, deferred,
-                       pairs - S, cnt, cand, hints);
+                       pairs - S, cnt, cand, hints, share);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // gapped pairs: the variant-5 walk with masked seasons (FOREMAST_HW_GAPS=v4: the variant-4
@@ -2517,9 +2657,11 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
 // pairs go to the variant-5 gapped kernel (hw_dg_kernel), which runs the same residual walk
 // with masked seasons.  `split_ws` (optional): int32 [2 * max_split] arrival counters
 // followed by float [max_split * 2 * 2 * CAND_FLOATS] candidates; the counters must be zero
-// on entry (they are left zero).
+// on entry (they are left zero).  `grid_quads`: G % 4 == 0 and grid rows 4q .. 4q + 3 carry
+// the same (alpha, beta), bit for bit (the caller checks it once per grid): hw_d_kernel then
+// walks season 1 once per (alpha, beta) (see QuadQueue).
 extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
-                                 int slots, hipStream_t st) {
+                                 int slots, hipStream_t st, int grid_quads) {
   const int K = a->K;
   if (!d_supported_k(K) || a->seg != 32 * K || a->m != a->seg || a->Tp % a->seg != 0 || a->Tp / a->seg < 2 ||
       a->Tp / a->seg > D_MAXSEG || !a->pair_tab || a->season_out || hmax < 1 || hmax > K || hmax > HALF_HB)
@@ -2531,11 +2673,11 @@ extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, i
   const GridSwitches sw = grid_switches();
   const auto launch = K == 45 ? (sw.prune ? launch_d_fit<45, true> : launch_d_fit<45, false>)
                               : (sw.prune ? launch_d_fit<9, true> : launch_d_fit<9, false>);
-  return (int)launch(a, hmax, deferred, split_ws, max_split, slots, sw.hints, st);
+  return (int)launch(a, hmax, deferred, split_ws, max_split, slots, sw.hints, (sw.share && grid_quads) ? 1 : 0, st);
 }
 
 extern "C" int fm_hw_d_fit(const SmoothArgs* a, int hmax, int* deferred, hipStream_t st) {
-  return fm_hw_d_fit_split(a, hmax, deferred, nullptr, 0, 0, st);
+  return fm_hw_d_fit_split(a, hmax, deferred, nullptr, 0, 0, st, 0);
 }
 
 template <int K, int MODE, typename TIN, int NC, int MINW, bool TAB = false>

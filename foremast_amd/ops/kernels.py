@@ -341,6 +341,27 @@ def pair_table(grid: torch.Tensor, K: int) -> torch.Tensor:
     return t
 
 
+_GRID_QUADS_CACHE: Dict[tuple, bool] = {}
+
+
+def grid_has_quads(grid: torch.Tensor) -> bool:
+    """Whether grid rows 4q .. 4q + 3 carry the same (alpha, beta), bit for bit, for every q
+    (and G % 4 == 0): ``hw_d_kernel`` then walks season 1 once per (alpha, beta).  Checked
+    once per grid (cached like :func:`pair_table`)."""
+    key = (grid.data_ptr(), tuple(grid.shape), grid.device)
+    hit = _GRID_QUADS_CACHE.get(key)
+    if hit is None:
+        G = grid.shape[0]
+        hit = False
+        if G > 0 and G % 4 == 0 and grid.dim() == 2 and grid.shape[1] >= 2:
+            ab = grid.detach()[:, :2].float().cpu().contiguous().view(torch.int32).view(G // 4, 4, 2)
+            hit = bool((ab == ab[:, :1]).all())
+        if len(_GRID_QUADS_CACHE) > 64:
+            _GRID_QUADS_CACHE.clear()
+        _GRID_QUADS_CACHE[key] = hit
+    return hit
+
+
 def smoothing_supported(mode: int, T: int, m: int, bf16: bool) -> bool:
     try:
         Tp, _, k, seg = smoothing_geometry(mode, T, m)
@@ -584,7 +605,7 @@ def _hw_half_fit(lib, hist, head, length, m, grid, det, Tp, pad, hmax, out, resi
         if os.environ.get("FOREMAST_HW_SPLIT", "1") == "0":
             slots = 0  # whole pairs only
         rc = lib.fm_hw_d_fit_split(a, int(hmax), nat.ptr(ws), nat.ptr(sws), SPLIT_MAX, slots,
-                                   nat.stream_handle(dev))
+                                   nat.stream_handle(dev), int(grid_has_quads(grid)))
         if rc != 0:
             ws.zero_()  # the general kernel did not run: its self-cleaning reset did not happen
         nat.check(rc, "fm_hw_d_fit_split")
