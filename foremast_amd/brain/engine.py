@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ..ingest.ringbuffer import HistoryRing, WindowRing
+from ..models import bivariate as biv_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
 from ..models import pairwise as pw_ref
@@ -139,6 +140,10 @@ class StreamingShard:
         self._cache: Optional[Dict] = None
         self._new_pts = 0          # points graduated into the history since the state was advanced
         self.last_refit = True     # whether the last score() refit the model
+        # joint bivariate normal over row pairs (set_pairs): scored after the per-row launch
+        self.pairs: Optional[np.ndarray] = None         # host [Np, 2] (row of metric 0, row of metric 1)
+        self._pairs_dev: Optional[torch.Tensor] = None
+        self._joint_out: Dict[str, torch.Tensor] = {}
 
     def refresh_thresholds(self) -> None:
         """Per-point thresholds of the full and the lowered (pairwise) band for the
@@ -154,6 +159,23 @@ class StreamingShard:
         if self.gpu:
             from ..ops import kernels as K
             self.anomalies = K.AnomalyBuffer(cap, self.device)
+
+    def set_pairs(self, pairs) -> None:
+        """Row pairs (metric 0, metric 1) scored jointly by the bivariate normal after the
+        per-row scorer (``models/bivariate.py``; GPU: ``ops/csrc/bivariate_pairs.hip``): a host
+        int array ``[Np, 2]``, or None for no joint model.  ``score()`` then adds
+        ``joint_verdict`` / ``joint_d2`` / ``joint_count`` / ``joint_mean`` / ``joint_cov``;
+        a flagged pair raises its first row's verdict (counted once per row in the per-app
+        table, not at all if the row was flagged already)."""
+        self._joint_out = {}
+        if pairs is None:
+            self.pairs = self._pairs_dev = None
+            return
+        p = np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), dtype=np.int32)
+        if p.size and (int(p.min()) < 0 or int(p.max()) >= self.spec.n_series):
+            raise ValueError(f"pair rows outside [0, {self.spec.n_series})")
+        self.pairs = p
+        self._pairs_dev = torch.from_numpy(p).to(self.device)
 
     # ------------------------------------------------------------------ data in
     def load_history(self, values: torch.Tensor) -> None:
@@ -403,7 +425,61 @@ class StreamingShard:
             out = self._score_cpu(cached)
         if self._cache is not None:
             self._cache["since"] = 0 if not cached else self._cache["since"] + 1
+        if self.pairs is not None:
+            # The joint pass is not part of tick_graph: the monitors that set pairs score the
+            # rows with moving_average_all, for which graph_ready() is never true.
+            self._score_joint(out)
         return out
+
+    def _score_joint(self, out: Dict[str, torch.Tensor]) -> None:
+        """The bivariate normal of every row pair, refitted from the ring like the per-row
+        scorers; threshold: the raw per-row one of the pair's first row (sigma units, not the
+        window-corrected thr_full), as BatchScorer.score_bivariate and the rollout engine."""
+        cfg, h = self.cfg, self.hist
+        # the per-row verdicts as the per-row scorer left them (jobs are judged by their own
+        # rows and their own pair; out["verdict"] feeds the health table)
+        rv = self._joint_out.get("row_verdict")
+        if rv is None:
+            rv = torch.empty_like(out["verdict"])
+        out["row_verdict"] = rv.copy_(out["verdict"])
+        if self.gpu:
+            from ..ops import kernels as K
+            j = K.bivariate_pairs(h.data, h.head, h.length, self._pairs_dev, self.cur.data, self.cur.P,
+                                  self.cur.W, self.threshold, min_valid=cfg.min_historical_points,
+                                  verdict=out["verdict"], app_id=self.app_id, app_stats=self.app_stats,
+                                  anomalies=self.anomalies, out=self._joint_out)
+        else:
+            j = self._joint_cpu(out)
+        j["row_verdict"] = rv
+        self._joint_out = j
+        for k in ("verdict", "d2", "count", "mean", "cov"):
+            out["joint_" + k] = j[k]
+
+    def _joint_cpu(self, out: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        cfg = self.cfg
+        pr = torch.from_numpy(self.pairs).long()
+        P, W = self.cur.P, self.cur.W
+        y = self.hist.logical().float()
+        fit = biv_ref.fit_bivariate(torch.stack([y[pr[:, 0]], y[pr[:, 1]]], 2))
+        cm = torch.nanmean(self.cur.data.view(-1, P, W), 1)          # pod means [N, W]
+        x = torch.stack([cm[pr[:, 0]], cm[pr[:, 1]]], 2)             # [Np, W, 2]
+        d2 = biv_ref.mahalanobis2(fit, x)
+        d2 = torch.where(torch.isnan(x).any(2), torch.full_like(d2, float("nan")), d2)
+        ok = fit.count >= cfg.min_historical_points
+        thr = self.threshold[pr[:, 0]].float()
+        valid = ~torch.isnan(d2)
+        flag = valid & ok[:, None] & (d2 > (thr * thr)[:, None])
+        count = flag.sum(1).int()
+        verdict = torch.where(count > 0, 1, torch.where(valid.any(1) & ok, 0, -1)).to(torch.int8)
+        score = torch.where(valid, d2.clamp(min=0).sqrt(), torch.zeros_like(d2)).amax(1)
+        rows = torch.unique(pr[verdict == 1, 0])
+        rv = out["verdict"]
+        new = rows[rv[rows] != 1]   # rows the per-row pass had not flagged: counted once each
+        rv[new] = 1
+        self.app_stats.index_put_((self.app_id[new].long(), torch.zeros_like(new)),
+                                  torch.ones_like(new, dtype=torch.int32), accumulate=True)
+        return {"mean": fit.mean, "cov": fit.cov, "nvalid": fit.count, "d2": d2, "count": count,
+                "verdict": verdict, "score": score}
 
     # ------------------------------------------------------------------ model cache
     def cache_supported(self) -> bool:

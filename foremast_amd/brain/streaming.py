@@ -25,7 +25,12 @@ series resident in one :class:`~foremast_amd.brain.engine.StreamingShard`:
   shards apps over GPU ranks, ``brain/node.py``); any anomalous series
   finishes its job ``completed_unhealth`` with the anomalous points; past
   ``endTime`` a job finishes ``completed_health``; band gauges are exported
-  for the UI; per-app counters feed the node health table.
+  for the UI; per-app counters feed the node health table;
+* joint model: under ``ML_ALGORITHM`` bivariate_normal / auto, a two-metric job's
+  rows also form a pair of the shard (``StreamingShard.set_pairs``): the bivariate
+  normal is refitted from the ring and scored on the window every tick in one more
+  launch, and a broken relation between the two metrics fails the job even when
+  each metric stays inside its own band.
 """
 
 from __future__ import annotations
@@ -149,6 +154,11 @@ class StreamingMonitor:
         self.ticks = 0
         self.history_queries = 0
         self._table: Optional[Dict[Tuple[str, str], native.KeyTable]] = None
+        # joint bivariate normal of two-metric jobs (plans.joint_kind == "biv"): derived from the
+        # jobs and their rows, rebuilt when either changes, never stored in a snapshot
+        self.pairs: List[Tuple[int, int]] = []       # distinct (row of alias 0, row of alias 1)
+        self.job_pair: Dict[str, int] = {}           # job id -> index into pairs
+        self._pairs_dirty = True
 
     # ------------------------------------------------------------------ membership
     def sync(self, steal_from=None) -> int:
@@ -170,6 +180,8 @@ class StreamingMonitor:
                 if key not in self.rows:
                     self.pending.add(key)
             self.jobs[d["id"]] = job
+        if docs:
+            self._pairs_dirty = True
         return len(docs)
 
     def release(self, pred: Callable[[Dict], bool]) -> int:
@@ -182,6 +194,8 @@ class StreamingMonitor:
                                   expect_claimed_by=self.worker_id)
                 del self.jobs[jid]
                 n += 1
+        if n:
+            self._pairs_dirty = True
         return n
 
     def live_keys(self) -> Set[Key]:
@@ -194,6 +208,8 @@ class StreamingMonitor:
     # ------------------------------------------------------------------ rows
     def _new_shard(self, capacity: int) -> StreamingShard:
         season = max(2, int(round(86400.0 / self.step)))
+        # the multi-metric algorithms (bivariate_normal, auto, lstm) score each row with
+        # moving_average_all; the bivariate normal's pairs come on top (_rebuild_pairs)
         algo = self.cfg.algorithm if self.cfg.algorithm in ("holt_winters", "exponential_smoothing",
                                                             "double_exponential_smoothing", "moving_average",
                                                             "moving_average_all", "seasonal_decompose",
@@ -230,6 +246,7 @@ class StreamingMonitor:
             new._refresh_horizons()
         self.keys.extend([None] * (capacity - len(self.keys)))
         self.shard = new
+        self._pairs_dirty = True  # the new shard has no pair table yet
 
     def _clear_rows(self, rows: List[int]) -> None:
         if not rows:
@@ -264,8 +281,31 @@ class StreamingMonitor:
             out.append((key, row))
         if dead or new:
             self._table = None
+            self._pairs_dirty = True
             self._refresh_apps()
         return out
+
+    def _rebuild_pairs(self) -> None:
+        """The shard's pair table from the live jobs: a job whose joint model is the
+        bivariate normal (``plans.joint_kind``) pairs the rows of its first two aliases in
+        sorted order, as ``worker.py`` ``_multivariate`` and ``rollout.py`` pair them.  Rows are
+        keyed by series, so jobs watching the same two series share one pair; a job whose two
+        aliases resolve to one series keeps the pair (row, row)."""
+        from .plans import joint_kind
+        self._pairs_dirty = False
+        index: Dict[Tuple[int, int], int] = {}
+        self.job_pair = {}
+        for jid, job in self.jobs.items():
+            if joint_kind(self.cfg.algorithm, len(job.series)) != "biv":
+                continue
+            a0, a1 = sorted(job.series)[:2]
+            r0, r1 = self.rows.get(job.series[a0]), self.rows.get(job.series[a1])
+            if r0 is None or r1 is None:
+                continue
+            self.job_pair[jid] = index.setdefault((r0, r1), len(index))
+        self.pairs = list(index)
+        if self.shard is not None:
+            self.shard.set_pairs(np.array(self.pairs, dtype=np.int32) if self.pairs else None)
 
     def _refresh_apps(self) -> None:
         """App roster of the live series (index = row of the per-app counters)."""
@@ -367,6 +407,8 @@ class StreamingMonitor:
         if assigned:
             failed = await self._load_history(assigned)
             self.pending -= {k for k, _ in assigned if k not in failed}
+        if self._pairs_dirty:
+            self._rebuild_pairs()
 
     async def _ingest_new(self, now: float) -> None:
         t_new = float(np.floor(now / self.step) * self.step)
@@ -402,6 +444,48 @@ class StreamingMonitor:
         self.t_last = t_new
 
     # ------------------------------------------------------------------ tick
+    def _band_points(self, out, verdict: np.ndarray, only: Optional[np.ndarray]):
+        """(rows, cols, values) of the window points outside their band on the flagged rows
+        (``only``: of these rows), from the bands instead of the compacted list."""
+        sh = self.shard
+        if only is None:
+            sel = slice(None)
+            base = np.arange(sh.spec.n_series)
+        else:
+            sel = torch.from_numpy(only).to(self.device)
+            base = only
+        x = sh.cur.data[sel].float().cpu().numpy()
+        up = out["upper"][sel].float().cpu().numpy()
+        lo = out["lower"][sel].float().cpu().numpy()
+        b = sh.bound[sel].cpu().numpy().astype(np.int64)[:, None]
+        flag = (((b & 1) != 0) & (x > up)) | (((b & 2) != 0) & (x < lo))
+        flag &= (verdict[base] == 1)[:, None]
+        rows, cols = np.nonzero(flag)
+        return base[rows], cols, x[rows, cols]
+
+    def _joint_points(self, out, col: int) -> Dict[int, List[float]]:
+        """Flagged pair -> its anomalous points ``[ts, v, ...]``: the slots whose squared
+        Mahalanobis distance exceeds the first row's raw threshold squared, dated by the slot's
+        age like the per-row points, valued by the pod mean of the first metric."""
+        jv = out["joint_verdict"].cpu().numpy()
+        hit = np.nonzero(jv == 1)[0]
+        if hit.size == 0:
+            return {}
+        sh = self.shard
+        idx = torch.from_numpy(hit).to(self.device)
+        r0 = torch.tensor([self.pairs[q][0] for q in hit.tolist()], dtype=torch.long, device=self.device)
+        d2 = out["joint_d2"][idx].float().cpu().numpy()
+        thr = sh.threshold[r0].float().cpu().numpy()
+        x = torch.nanmean(sh.cur.data[r0].view(len(hit), sh.cur.P, self.W), 1).cpu().numpy()
+        res: Dict[int, List[float]] = {}
+        with np.errstate(invalid="ignore"):
+            flag = d2 > (thr * thr)[:, None]
+        for i, q in enumerate(hit.tolist()):
+            pts = sorted((self.t_last - ((col - c) % self.W) * self.step, float(x[i, c]))
+                         for c in np.nonzero(flag[i])[0].tolist())
+            res[q] = [v for p in pts for v in p]
+        return res
+
     async def tick(self) -> Dict[str, str]:
         """One scoring tick over every continuous series; returns job → status written."""
         await self._apply_changes()
@@ -416,23 +500,27 @@ class StreamingMonitor:
         out = self.shard.score()
         C = self.W
         col = (self.shard.cur.ticks - 1) % C
-        verdict = out["verdict"].cpu().numpy()
+        # with a pair table the shard's "verdict" also holds the rows the joint model raised (the
+        # health table's view); a job is judged by its own rows ("row_verdict") and its own pair
+        verdict = out["row_verdict" if "joint_verdict" in out else "verdict"].cpu().numpy()
         upper = out["upper"][:, col].float().cpu().numpy() if "upper" in out else None
         lower = out["lower"][:, col].float().cpu().numpy() if "lower" in out else None
         points: Dict[int, List[Tuple[float, float]]] = {}
+        joint = self._joint_points(out, col) if "joint_verdict" in out else {}
         ab = self.shard.anomalies
         overflow = False
         if ab is not None:  # K9 device-side compaction: only the anomalies come back
             rows, cols, vals, overflow = ab.fetch()
+            # the list also holds the joint model's triples under each flagged pair's first row:
+            # a row flagged by both takes its per-row points from the bands below
+            both = sorted({self.pairs[q][0] for q in joint if verdict[self.pairs[q][0]] == 1})
+            if both and not overflow:
+                keep = ~np.isin(rows, both)
+                r2, c2, v2 = self._band_points(out, verdict, np.array(both, dtype=np.int64))
+                rows, cols, vals = (np.concatenate([rows[keep], r2]), np.concatenate([cols[keep], c2]),
+                                    np.concatenate([vals[keep], v2]))
         if ab is None or overflow:
-            x = self.shard.cur.data.float().cpu().numpy()
-            up = out["upper"].float().cpu().numpy()
-            lo = out["lower"].float().cpu().numpy()
-            b = self.shard.bound.cpu().numpy().astype(np.int64)[:, None]
-            flag = (((b & 1) != 0) & (x > up)) | (((b & 2) != 0) & (x < lo))
-            flag &= (verdict == 1)[:, None]
-            rows, cols = np.nonzero(flag)
-            vals = x[rows, cols]
+            rows, cols, vals = self._band_points(out, verdict, None)
         for rr, cc, vv in zip(rows.tolist(), cols.tolist(), vals.tolist()):
             age = (col - cc) % C
             points.setdefault(rr, []).append((self.t_last - age * self.step, vv))
@@ -454,6 +542,10 @@ class StreamingMonitor:
                     for ts, v in sorted(points.get(row, [])):
                         flat += [ts, float(v)]
                     anomaly[alias] = {"tags": "", "values": flat}
+            q = self.job_pair.get(jid)
+            if q in joint:
+                # the joint points replace the first alias's own list (worker.py _multivariate)
+                anomaly[sorted(job.series)[0]] = {"tags": "", "values": joint[q]}
             if anomaly:
                 status, reason = r.ST_COMPLETED_UNHEALTH, "anomaly detected in " + ",".join(sorted(anomaly))
             elif now >= job.end_ts:
@@ -469,6 +561,7 @@ class StreamingMonitor:
             ok = self.store.update(jid, fields, expect_claimed_by=self.worker_id)
             if not ok or status in r.TERMINAL_STATUSES:
                 del self.jobs[jid]  # finished, or another worker took the lease
+                self._pairs_dirty = True
                 if ok:
                     self.metrics.jobs.labels(status=status).inc()
             written[jid] = status
@@ -523,6 +616,7 @@ class StreamingMonitor:
         self.keys, self.rows, self.pending = keys, snap_rows, set()
         self._table = None
         self._refresh_apps()
+        self._rebuild_pairs()  # derived state: not in the snapshot
         return True
 
     async def run_forever(self, stop: Optional[asyncio.Event] = None, period: Optional[float] = None,

@@ -10,6 +10,7 @@ extern "C" long long fm_abi_sizeof(const char* name) {
   if (!__builtin_strcmp(name, "RankArgs")) return sizeof(RankArgs);
   if (!__builtin_strcmp(name, "WindowArgs")) return sizeof(WindowArgs);
   if (!__builtin_strcmp(name, "BivArgs")) return sizeof(BivArgs);
+  if (!__builtin_strcmp(name, "BivPairArgs")) return sizeof(BivPairArgs);
   return -1;
 }
 
@@ -22,5 +23,6 @@ extern "C" long long fm_abi_offsetof(const char* name, const char* field) {
   if (!__builtin_strcmp(name, "RankArgs")) { FM_OFF(RankArgs, pvals); FM_OFF(RankArgs, alpha); FM_OFF(RankArgs, p_friedman); FM_OFF(RankArgs, pods_b); FM_OFF(RankArgs, z_crit); }
   if (!__builtin_strcmp(name, "WindowArgs")) { FM_OFF(WindowArgs, det); }
   if (!__builtin_strcmp(name, "BivArgs")) { FM_OFF(BivArgs, eps); FM_OFF(BivArgs, app_stats); }
+  if (!__builtin_strcmp(name, "BivPairArgs")) { FM_OFF(BivPairArgs, threshold); FM_OFF(BivPairArgs, anom_val); }
   return -1;
 }

@@ -155,3 +155,42 @@ struct BivArgs {
   const int* app_id;
   int* app_stats;
 };
+
+// K8 over row pairs of ONE ring (streaming shard): both metrics of a pair are rows of
+// `hist`, the current values are pod means over the [N, P*W] window ring.
+struct BivPairArgs {
+  const void* hist;       // [N, ld] ring (float or bf16)
+  long long ld;
+  int ring_len;
+  int head;
+  int len;
+  int N;
+  const int* pairs;       // [Np, 2] (row of metric 0, row of metric 1)
+  int Np;
+  int P;                  // pods per window slot
+  const float* cur;       // [N, ld_cur], column p * W + slot
+  long long ld_cur;
+  int W;
+  int min_valid;
+  const float* threshold; // [N] raw sigma units, read at the pair's first row
+  float eps;
+  int anom_cap;
+  float* mean;            // [Np, 2]
+  float* cov;             // [Np, 3]
+  float* nvalid;          // [Np]
+  float* d2;              // [Np, W]
+  int* count;             // [Np]
+  signed char* verdict;   // [Np]
+  float* score;           // [Np] max d
+  // shard state (optional): a flagged pair raises its first row's verdict, counted once
+  // per row and tick in app_stats[2 * app_id[row]] unless the row was flagged already
+  signed char* row_verdict; // [N] or null
+  const int* app_id;        // [N] or null
+  int* app_stats;           // [A, 2] or null
+  int* raised;              // [N] scratch, zeroed by the caller (needed with row_verdict)
+  // K9 compaction (optional, DetectArgs' protocol): (first row, slot, pod mean of metric 0)
+  int* anom_count;
+  int* anom_series;
+  int* anom_col;
+  float* anom_val;
+};

@@ -835,6 +835,85 @@ def bivariate(hx: torch.Tensor, hy: torch.Tensor, head: int, length: int, cur: t
     return out
 
 
+def bivariate_pairs(hist: torch.Tensor, head: int, length: int, pairs, cur: torch.Tensor, pods: int, window: int,
+                    threshold: torch.Tensor, *, min_valid: int = 0, eps: float = 1e-9,
+                    verdict: Optional[torch.Tensor] = None, app_id: Optional[torch.Tensor] = None,
+                    app_stats: Optional[torch.Tensor] = None, anomalies: Optional[AnomalyBuffer] = None,
+                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """K8 over row pairs of one ring (``bivariate_pairs.hip``).  ``pairs``: ``[Np, 2]`` rows
+    (metric 0, metric 1) of ``hist`` -- an int32 GPU tensor, or a numpy / CPU array, which is
+    range-checked here and copied to the device; ``cur``: the ``[N, pods * window]`` window
+    ring; ``threshold``: raw sigma units per row, read at a pair's first row.  ``verdict``
+    (int8 ``[N]``, the shard's row verdicts), ``app_id`` / ``app_stats`` and ``anomalies``
+    receive the effects of the flagged pairs.  Outputs in ``out``: ``mean [Np, 2]``, ``cov
+    [Np, 3]``, ``nvalid``, ``d2 [Np, window]``, ``count``, ``verdict``, ``score``."""
+    lib = nat.require()
+    _hist_check(hist, head, length)
+    dev = hist.device
+    N = hist.shape[0]
+    P, W = int(pods), int(window)
+    _need(P >= 1 and W >= 1, "pods and window must be >= 1")
+    if not isinstance(pairs, torch.Tensor) or not pairs.is_cuda:
+        import numpy as np
+        host = pairs.numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+        host = host.reshape(-1, 2) if host.size == 0 else host
+        _need(host.ndim == 2 and host.shape[1] == 2 and host.dtype.kind in "iu", "pairs must be integer [Np, 2]")
+        _need(host.size == 0 or (int(host.min()) >= 0 and int(host.max()) < N), f"pair rows outside [0, {N})")
+        pairs = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev)
+    _need(pairs.dim() == 2 and pairs.shape[1] == 2 and pairs.dtype == torch.int32 and pairs.is_contiguous()
+          and pairs.device == dev, "pairs must be contiguous int32 [Np, 2] on the ring's device")
+    Np = pairs.shape[0]
+    _need(cur.dim() == 2 and cur.shape[0] == N and cur.shape[1] == P * W,
+          f"cur must be [{N}, {P * W}], got {tuple(cur.shape)}")
+    _need(cur.dtype == torch.float32 and cur.stride(1) == 1 and cur.device == dev,
+          "cur must be float32 with unit inner stride on the ring's device")
+    _vec(threshold, N, torch.float32, "threshold", dev)
+    _vec(verdict, N, torch.int8, "verdict", dev)
+    _vec(app_id, N, torch.int32, "app_id", dev)
+    if app_id is not None:
+        _need(verdict is not None, "app_id needs the row verdicts")
+        _need(app_stats is not None and app_stats.dtype == torch.int32 and app_stats.is_contiguous()
+              and app_stats.dim() == 2 and app_stats.shape[1] == 2 and app_stats.device == dev,
+              "app_stats must be contiguous int32 [A, 2]")
+    out = {} if out is None else out
+    shapes = {"mean": ((Np, 2), torch.float32), "cov": ((Np, 3), torch.float32), "nvalid": ((Np,), torch.float32),
+              "d2": ((Np, W), torch.float32), "count": ((Np,), torch.int32), "verdict": ((Np,), torch.int8),
+              "score": ((Np,), torch.float32)}
+    for k, (shape, dt) in shapes.items():
+        if k not in out or tuple(out[k].shape) != shape:
+            out[k] = torch.empty(shape, dtype=dt, device=dev)
+    if verdict is not None:
+        if "raised" not in out or out["raised"].shape[0] != N:
+            out["raised"] = torch.empty(N, dtype=torch.int32, device=dev)
+        out["raised"].zero_()
+    if Np == 0:
+        return out
+    a = nat.BivPairArgs()
+    a.hist = nat.ptr(hist)
+    a.ld = hist.stride(0)
+    a.ring_len = hist.shape[1]
+    a.head, a.len, a.N = int(head), int(length), N
+    a.pairs, a.Np, a.P = nat.ptr(pairs), Np, P
+    a.cur, a.ld_cur, a.W = nat.ptr(cur), cur.stride(0), W
+    a.min_valid = int(min_valid)
+    a.threshold = nat.ptr(threshold)
+    a.eps = float(eps)
+    for k in shapes:
+        setattr(a, k, nat.ptr(out[k]))
+    a.row_verdict = nat.ptr(verdict)
+    a.app_id = nat.ptr(app_id)
+    a.app_stats = nat.ptr(app_stats) if app_id is not None else 0
+    a.raised = nat.ptr(out["raised"]) if verdict is not None else 0
+    if anomalies is not None:
+        _need(anomalies.count.device == dev, "anomaly buffer on wrong device")
+        a.anom_count, a.anom_series, a.anom_col, a.anom_val = (nat.ptr(anomalies.count), nat.ptr(anomalies.series),
+                                                               nat.ptr(anomalies.col), nat.ptr(anomalies.val))
+        a.anom_cap = anomalies.cap
+    nat.check(lib.fm_bivariate_pairs(a, int(hist.dtype == torch.bfloat16), nat.stream_handle(dev)),
+              "fm_bivariate_pairs")
+    return out
+
+
 def ring_append(dst: torch.Tensor, col0: int, src: torch.Tensor, col_dev: Optional[torch.Tensor] = None) -> None:
     """``dst[n, (col0 + j) % R] = src[n, j]`` (dst may be float32 or bf16); ``col_dev``
     (int32 device scalar): added to ``col0`` on the device (graph-captured ticks)."""
