@@ -120,7 +120,8 @@ class LstmMonitor:
         self.F = int(features)
         R = ring_len or self.cfg.ring_len
         self.history = history or ResidentHistory(self.prom, self.device, R, self.step, clock=clock,
-                                                  decode_threads=decode_threads)
+                                                  decode_threads=decode_threads,
+                                                  dtype=self.cfg.ring_dtype(self.device))
         if fp8 is None:
             fp8 = os.environ.get("FOREMAST_LSTM_FP8", "0") not in ("0", "", "false")
         tb = train_batch if self.gpu else min(train_batch, 64)

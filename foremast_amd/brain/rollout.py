@@ -236,7 +236,8 @@ class RolloutMonitor:
         self.claim_limit = claim_limit
         self.history = history or ResidentHistory(self.prom, self.device, ring_len or self.cfg.ring_len, self.step,
                                                   clock=clock, decode_threads=decode_threads,
-                                                  apps_per_query=apps_per_query)
+                                                  apps_per_query=apps_per_query,
+                                                  dtype=self.cfg.ring_dtype(self.device))
         self.min_capacity = max(1, int(min_capacity))
         self.jobs: Dict[str, RolloutPlan] = {}        # admitted (rows assigned)
         self.waiting: Dict[str, RolloutPlan] = {}     # claimed, history not resident yet

@@ -222,8 +222,11 @@ class StreamingMonitor:
         if algo == "prophet" and self.R < 2:
             algo = "moving_average_all"
         dev = self.device
+        # FOREMAST_DTYPE, unless a shard is already resident (a restored snapshot keeps its
+        # ring dtype when it grows)
+        dtype = self.shard.spec.dtype if self.shard is not None else self.cfg.ring_dtype(dev)
         spec = ShardSpec(n_series=capacity, ring_len=self.R, season=season, pods=1, window=self.W, algorithm=algo,
-                         pairwise="NONE", dtype=torch.bfloat16 if dev.type == "cuda" else torch.float32,
+                         pairwise="NONE", dtype=dtype,
                          n_apps=max(1, len(self.apps)))
         sh = StreamingShard(spec, self.cfg, dev)
         sh.hist.state.head, sh.hist.state.length = 0, self.R   # rows start all-NaN (free)
@@ -611,6 +614,9 @@ class StreamingMonitor:
         if (set(snap_rows) != self.live_keys() or ex.get("step") != self.step or shard.spec.ring_len != self.R
                 or shard.spec.window != self.W or self.clock() - float(ex.get("t_last", 0)) > self.R * self.step / 2):
             return False
+        if shard.spec.dtype != self.cfg.ring_dtype(self.device):
+            log.info("snapshot %s holds %s rings, FOREMAST_DTYPE=%s asks for %s: keeping the snapshot's", path,
+                     shard.spec.dtype, self.cfg.dtype, self.cfg.ring_dtype(self.device))
         shard.enable_anomaly_list(cap=max(1024, 4 * len(keys)))
         self.shard, self.t_last = shard, float(ex["t_last"])
         self.keys, self.rows, self.pending = keys, snap_rows, set()

@@ -120,6 +120,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.fm_hw_q_lds_bytes.restype = C.c_size_t
     lib.fm_hw_q_fit.argtypes = [C.POINTER(SmoothArgs), P, I, P, P]
     lib.fm_hw_q_fit.restype = I
+    # variant 5 with the ring's element type as the last argument (0: bf16, 1: fp32)
+    lib.fm_hw_d_fit_split_dt.argtypes = [C.POINTER(SmoothArgs), I, P, P, I, I, P, I, I]
+    lib.fm_hw_d_fit_split_dt.restype = I
+    lib.fm_hw_q_fit_dt.argtypes = [C.POINTER(SmoothArgs), P, I, P, P, I]
+    lib.fm_hw_q_fit_dt.restype = I
     lib.fm_hw_d_split_plan.argtypes = [I, I, I]
     lib.fm_hw_d_split_plan.restype = I
     lib.fm_es_seq_fit.argtypes = [C.POINTER(SmoothArgs), I, I, P]

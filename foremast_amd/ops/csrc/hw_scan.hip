@@ -1355,23 +1355,47 @@ __device__ __forceinline__ void d_lds_init(const DLds<K, S>& L, const SmoothArgs
 // load per season, no per-element address math; otherwise one clamped 2-byte load per
 // element.  Padding (before the series' start) is NaN; the padding series of a short last
 // group (!real) is zeros, which keeps the group on the fast path.
-__device__ __forceinline__ void stage_load(const bf16_t* row, bool real, bool al, int o0, int head, int nseg, int m,
+// T is the ring's element type (bf16_t or float).  An fp32 ring's aligned chunk is 32 bytes
+// at a 16-byte aligned address (the row base need not be 32-byte aligned): two 16-byte loads
+// straight into y[k], nothing to unpack; unaligned, one clamped 4-byte load per element.
+
+// 8 consecutive fp32 ring columns from a 16-byte aligned address into v (zeros if !on)
+__device__ __forceinline__ void load8_f32(const float* p, bool on, float (&v)[8]) {
+  float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+  if (on) {
+    lo = *(const float4*)p;
+    hi = *(const float4*)(p + 4);
+  }
+  v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
+  v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+}
+
+template <typename T>
+__device__ __forceinline__ void stage_load(const T* row, bool real, bool al, int o0, int head, int nseg, int m,
                                            int R, int pad, float (&y)[D_MAXSEG][8]) {
+  static_assert(std::is_same<T, bf16_t>::value || std::is_same<T, float>::value, "ring element type");
   if (al) {
 #pragma unroll
     for (int k = 0; k < D_MAXSEG; ++k) {
       const int t0 = k * m + o0 - pad;  // logical index of element 0 (multiple-of-8 column)
       int c = (head + t0) % R;
       c += c < 0 ? R : 0;
-      uint4 w = make_uint4(0u, 0u, 0u, 0u);
-      if (k < nseg) w = *(const uint4*)(row + c);  // k < nseg is block-uniform
-      const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const unsigned x = ww[u >> 1];
-        const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
+      if constexpr (std::is_same<T, float>::value) {
+        load8_f32(row + c, k < nseg, y[k]);  // k < nseg is block-uniform
         const bool ok = real && k < nseg;
-        y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) y[k][u] = ok ? (t0 + u >= 0 ? y[k][u] : fm_nan()) : 0.f;
+      } else {
+        uint4 w = make_uint4(0u, 0u, 0u, 0u);
+        if (k < nseg) w = *(const uint4*)(row + c);  // k < nseg is block-uniform
+        const unsigned ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const unsigned x = ww[u >> 1];
+          const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
+          const bool ok = real && k < nseg;
+          y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
+        }
       }
     }
   } else {
@@ -1386,7 +1410,7 @@ __device__ __forceinline__ void stage_load(const bf16_t* row, bool real, bool al
         const bool pos = t >= 0;
         int c = head + ((ok && pos) ? t : 0);
         c -= (c >= R) ? R : 0;
-        const float v = bf16_to_f32(row[c]);
+        const float v = to_f32<T>(row[c]);
         y[k][u] = ok ? (pos ? v : fm_nan()) : 0.f;
       }
     }
@@ -1459,7 +1483,7 @@ __device__ __forceinline__ void stage_scatter(const DLds<K, S>& L, int nseg, int
 // at once; then the season-0 / season-1 sums and counts of each series to this wave's stat
 // slots.  The slots are summed in wave order (d_means): a float atomicAdd's order would make
 // l0 / b0 (and a beta = 0 fit's trend) differ in the last bit from run to run.
-template <int K, int S>
+template <typename T, int K, int S>
 __device__ __forceinline__ void d_stage(const DLds<K, S>& L, const SmoothArgs& a, int n0, int head, int tid, int lane,
                                         int w, int& bad) {
   constexpr int GRP = 8;
@@ -1477,7 +1501,7 @@ __device__ __forceinline__ void d_stage(const DLds<K, S>& L, const SmoothArgs& a
     const int o0 = ostart + (g - r * ngrp) * GRP;
     const int n = n0 + r;
     const bool real = n < a.N;
-    const bf16_t* row = (const bf16_t*)a.hist + (long long)(real ? n : 0) * a.ld;
+    const T* row = (const T*)a.hist + (long long)(real ? n : 0) * a.ld;
     float y[D_MAXSEG][GRP];
     stage_load(row, real, al, o0, head, nseg, m, R, a.pad, y);
     stage_scatter(L, nseg, m, r, o0, y, acc, bad);
@@ -1639,7 +1663,7 @@ __device__ __forceinline__ void finish_series(const SmoothArgs& a, int n, int la
 // `hid`), and whichever half arrives second merges the two and finishes the series.
 constexpr int CAND_FLOATS = 4 + HALF_HB;  // SSE, index bits, level, trend, seasonal phases
 
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T>
 __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0, int* deferred, int pi_lo,
                                            int pi_hi, int slot, int hid, int* cnt, float* cand, int hints,
                                            int share) {
@@ -1666,7 +1690,7 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
   __syncthreads();
 
   int bad = 0;
-  d_stage(L, a, n0, head, tid, lane, w, bad);
+  d_stage<T>(L, a, n0, head, tid, lane, w, bad);
   if (bad) atomicOr(L.flag, 1);
   __syncthreads();
   if (*L.flag) {  // block-uniform: a gap past season 0 — the gapped kernel takes the pair
@@ -1826,18 +1850,18 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
 
 // Workgroups [0, n_full) fit whole series pairs 0..n_full-1; the rest are split-tail
 // halves: workgroup n_full + 2 s + h fits half h of the grid of pair n_full + s.
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T = bf16_t>
 __global__ __launch_bounds__(256, 2) void hw_d_kernel(const SmoothArgs a, int hmax, int* deferred, int n_full,
                                                      int* cnt, float* cand, int hints, int share) {
   const int b = blockIdx.x;
   const int npairs = (a.G + 1) / 2;
   if (b < n_full) {
-    hw_d_block<K, PRUNE>(a, hmax, 2 * b, deferred, 0, npairs, -1, 0, cnt, cand, hints, share);
+    hw_d_block<K, PRUNE, T>(a, hmax, 2 * b, deferred, 0, npairs, -1, 0, cnt, cand, hints, share);
     return;
   }
   const int item = b - n_full, slot = item >> 1, h = item & 1, mid = npairs / 2;
-  hw_d_block<K, PRUNE>(a, hmax, 2 * (n_full + slot), deferred, h ? mid : 0, h ? npairs : mid, slot, h, cnt, cand,
-                       hints, share);
+  hw_d_block<K, PRUNE, T>(a, hmax, 2 * (n_full + slot), deferred, h ? mid : 0, h ? npairs : mid, slot, h, cnt, cand,
+                          hints, share);
 }
 
 
@@ -1852,7 +1876,7 @@ __global__ __launch_bounds__(256, 2) void hw_d_kernel(const SmoothArgs a, int hm
 // launched with its own pair table); the hints are those of the first two series (the
 // branch and bound is exact in any order).
 constexpr int Q_S = 4;  // series per wave / workgroup
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T>
 __device__ __forceinline__ void hw_q_block(const SmoothArgs& a, int hmax, int n0, int* deferred, int hints) {
   using Lds = DLds<K, Q_S>;
   constexpr int SEA = Lds::SEA;
@@ -1883,7 +1907,7 @@ __device__ __forceinline__ void hw_q_block(const SmoothArgs& a, int hmax, int n0
   __syncthreads();
 
   int bad = 0;
-  d_stage(L, a, n0, head, tid, lane, w, bad);
+  d_stage<T>(L, a, n0, head, tid, lane, w, bad);
   if (bad) atomicOr(L.flag, 1);
   __syncthreads();
   if (*L.flag) {  // block-uniform: a gap past season 0 — the 32-lane gapped kernel takes both pairs
@@ -1970,9 +1994,9 @@ __device__ __forceinline__ void hw_q_block(const SmoothArgs& a, int hmax, int n0
                 (float)(ns1 * m));
 }
 
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T = bf16_t>
 __global__ __launch_bounds__(256, 2) void hw_q_kernel(const SmoothArgs a, int hmax, int* deferred, int hints) {
-  hw_q_block<K, PRUNE>(a, hmax, 4 * blockIdx.x, deferred, hints);
+  hw_q_block<K, PRUNE, T>(a, hmax, 4 * blockIdx.x, deferred, hints);
 }
 
 // ---- variant 5, gapped series: hw_dg_kernel ------------------------------------------------
@@ -2079,7 +2103,7 @@ __device__ __forceinline__ void dg_season(bool m2, bool r1, const float* blk, v2
                                  nullptr, k2lo, k2hi, k1lo, k1hi);
 }
 
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T>
 __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n0, int hints, int* gflags) {
   using Lds = DLds<K, 2>;
   constexpr int SEA = Lds::SEA;
@@ -2121,7 +2145,7 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
       const int r = g >= ngrp ? 1 : 0, o0 = ostart + (g - r * ngrp) * GRP;
       const int n = n0 + r;
       const bool real = n < a.N;
-      const bf16_t* row = (const bf16_t*)a.hist + (long long)(real ? n : 0) * a.ld;
+      const T* row = (const T*)a.hist + (long long)(real ? n : 0) * a.ld;
       float y[D_MAXSEG][GRP];
       if (al) {
 #pragma unroll
@@ -2129,15 +2153,22 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
           const int t0 = k * m + o0 - a.pad;
           int c = (head + t0) % R;
           c += c < 0 ? R : 0;
-          uint4 wv = make_uint4(0u, 0u, 0u, 0u);
-          if (k < nseg) wv = *(const uint4*)(row + c);
-          const unsigned ww[4] = {wv.x, wv.y, wv.z, wv.w};
-#pragma unroll
-          for (int u = 0; u < GRP; ++u) {
-            const unsigned x = ww[u >> 1];
-            const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
+          if constexpr (std::is_same<T, float>::value) {  // fp32 ring: two 16-byte loads, see stage_load
+            load8_f32(row + c, k < nseg, y[k]);
             const bool ok = real && k < nseg;
-            y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
+#pragma unroll
+            for (int u = 0; u < GRP; ++u) y[k][u] = ok ? (t0 + u >= 0 ? y[k][u] : fm_nan()) : 0.f;
+          } else {
+            uint4 wv = make_uint4(0u, 0u, 0u, 0u);
+            if (k < nseg) wv = *(const uint4*)(row + c);
+            const unsigned ww[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+            for (int u = 0; u < GRP; ++u) {
+              const unsigned x = ww[u >> 1];
+              const float v = __uint_as_float((u & 1) ? (x & 0xffff0000u) : (x << 16));
+              const bool ok = real && k < nseg;
+              y[k][u] = ok ? (t0 + u >= 0 ? v : fm_nan()) : 0.f;
+            }
           }
         }
       } else {
@@ -2150,7 +2181,7 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
             const bool pos = t >= 0;
             int c = head + ((ok && pos) ? t : 0);
             c -= (c >= R) ? R : 0;
-            const float v = bf16_to_f32(row[c]);
+            const float v = to_f32<T>(row[c]);
             y[k][u] = ok ? (pos ? v : fm_nan()) : 0.f;
           }
         }
@@ -2405,7 +2436,7 @@ __device__ __forceinline__ void hw_dg_block(const SmoothArgs& a, int hmax, int n
 // pairs since allocation, for the records) and resets count, done and the queue.  A pair's
 // flag is set by hw_d_kernel when it defers the pair and cleared here when the pair is found
 // gap-free; hw_d_kernel hands flagged pairs over without staging them.
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T = bf16_t>
 __global__ __launch_bounds__(256, 2) void hw_dg_kernel(const SmoothArgs a, int hmax, int* deferred, int hints) {
   const int cnt = min(deferred[0], (a.N + 1) / 2);
   if (cnt == 0) return;  // gap-free shard: count and done are already 0
@@ -2425,7 +2456,7 @@ __global__ __launch_bounds__(256, 2) void hw_dg_kernel(const SmoothArgs a, int h
         (const __attribute__((address_space(4))) SmoothArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     int hm = hmax, hi = hints;
     asm volatile("" : "+s"(ap), "+s"(hm), "+s"(hi));
-    hw_dg_block<K, PRUNE>(*(const SmoothArgs*)ap, hm, deferred[1 + q], hi, done + 3);
+    hw_dg_block<K, PRUNE, T>(*(const SmoothArgs*)ap, hm, deferred[1 + q], hi, done + 3);
     __syncthreads();  // LDS is reused by the next pair
   }
   if (threadIdx.x == 0) {
@@ -2499,14 +2530,14 @@ static GridSwitches grid_switches() {
   return s;
 }
 
-template <bool PRUNE>
+template <bool PRUNE, typename T>
 static hipError_t launch_q_fit(const SmoothArgs* a, const float* tab_g, int hmax, int* deferred, int hints,
                                hipStream_t st) {
   const int K = a->K;
   const size_t lds = fm_hw_q_lds_bytes(a->Tp, a->seg, K);
   const size_t dlds = fm_hw_dg_lds_bytes(a->Tp, a->seg, K / 2);
   const int quads = (a->N + 3) / 4;
-  hipLaunchKernelGGL((hw_q_kernel<18, PRUNE>), dim3(quads), dim3(256), lds, st, *a, hmax, deferred, hints);
+  hipLaunchKernelGGL((hw_q_kernel<18, PRUNE, T>), dim3(quads), dim3(256), lds, st, *a, hmax, deferred, hints);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   SmoothArgs ag = *a;
@@ -2514,14 +2545,16 @@ static hipError_t launch_q_fit(const SmoothArgs* a, const float* tab_g, int hmax
   ag.K = K / 2;
   const int pairs = (a->N + 1) / 2;
   const int grid = pairs < 512 ? pairs : 512;
-  hipLaunchKernelGGL((hw_dg_kernel<9, PRUNE>), dim3(grid), dim3(256), dlds, st, ag, hmax, deferred, hints);
+  hipLaunchKernelGGL((hw_dg_kernel<9, PRUNE, T>), dim3(grid), dim3(256), dlds, st, ag, hmax, deferred, hints);
   return hipGetLastError();
 }
 
 // Variant 5 at m = 16 K: hw_q_kernel over quads, then the gapped kernel at K / 2 (32 lanes x
 // K / 2 steps) over the pairs it deferred, with `tab_g` = pair_table(grid, K / 2) (the
 // 32-lane kernel's weights and powers).  Same workspace and contract as fm_hw_d_fit.
-extern "C" int fm_hw_q_fit(const SmoothArgs* a, const float* tab_g, int hmax, int* deferred, hipStream_t st) {
+// `fp32`: the ring's element type (0: bf16, else fp32).
+extern "C" int fm_hw_q_fit_dt(const SmoothArgs* a, const float* tab_g, int hmax, int* deferred, hipStream_t st,
+                              int fp32) {
   const int K = a->K;
   if (!q_supported_k(K) || a->seg != 16 * K || a->m != a->seg || a->Tp % a->seg != 0 || a->Tp / a->seg < 2 ||
       a->Tp / a->seg > D_MAXSEG || !a->pair_tab || !tab_g || a->season_out || hmax < 1 || hmax > K ||
@@ -2532,8 +2565,13 @@ extern "C" int fm_hw_q_fit(const SmoothArgs* a, const float* tab_g, int hmax, in
     return (int)hipErrorNotSupported;
   if (!deferred) return (int)hipErrorInvalidValue;
   const GridSwitches sw = grid_switches();
-  return (int)(sw.prune ? launch_q_fit<true>(a, tab_g, hmax, deferred, sw.hints, st)
-                        : launch_q_fit<false>(a, tab_g, hmax, deferred, sw.hints, st));
+  const auto launch = fp32 ? (sw.prune ? launch_q_fit<true, float> : launch_q_fit<false, float>)
+                           : (sw.prune ? launch_q_fit<true, bf16_t> : launch_q_fit<false, bf16_t>);
+  return (int)launch(a, tab_g, hmax, deferred, sw.hints, st);
+}
+
+extern "C" int fm_hw_q_fit(const SmoothArgs* a, const float* tab_g, int hmax, int* deferred, hipStream_t st) {
+  return fm_hw_q_fit_dt(a, tab_g, hmax, deferred, st, 0);
 }
 
 // Deferred detection for HW variants 4/5: band, verdict, per-app counters and the K9
@@ -2617,7 +2655,7 @@ extern "C" int fm_hw_d_split_plan(int pairs, int slots, int max_split) {
   return best;
 }
 
-template <int K, bool PRUNE>
+template <int K, bool PRUNE, typename T>
 static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split, int slots,
                                int hints, int share, hipStream_t st) {
   const size_t lds = fm_hw_d_lds_bytes(a->Tp, a->seg, K);
@@ -2631,14 +2669,14 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
   if (da && da[0] == '1')
     hipLaunchKernelGGL(hw_dg_list_all_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, deferred, pairs);
   else
-    hipLaunchKernelGGL((hw_d_kernel<K, PRUNE>), dim3(pairs - S + 2 * S), dim3(256), lds, st, *a, hmax, deferred,
+    hipLaunchKernelGGL((hw_d_kernel<K, PRUNE, T>), dim3(pairs - S + 2 * S), dim3(256), lds, st, *a, hmax, deferred,
                        pairs - S, cnt, cand, hints, share);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // gapped pairs: the variant-5 walk with masked seasons (FOREMAST_HW_GAPS=v4: the variant-4
-  // general kernel instead, for A/B runs; daily season at 60 s only)
+  // general kernel instead, for A/B runs; daily season at 60 s and bf16 rings only)
   const char* ge = getenv("FOREMAST_HW_GAPS");
-  if (K == 45 && ge && ge[0] == 'v') {
+  if (K == 45 && std::is_same<T, bf16_t>::value && ge && ge[0] == 'v') {
     const size_t glds = fm_hw_half_lds_bytes(a->Tp, a->seg, K);
     if (glds > 64 * 1024) return hipErrorNotSupported;
     hipLaunchKernelGGL((hw_half_general_kernel<45>), dim3(pairs < 512 ? pairs : 512), dim3(256), glds, st, *a, hmax,
@@ -2649,7 +2687,7 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
   int grid = pairs < 512 ? pairs : 512;
   const char* gg = getenv("FOREMAST_HW_DG_GRID");  // A/B: workgroups of the gapped kernel
   if (gg && atoi(gg) > 0) grid = atoi(gg) < pairs ? atoi(gg) : pairs;
-  hipLaunchKernelGGL((hw_dg_kernel<K, PRUNE>), dim3(grid), dim3(256), dlds, st, *a, hmax, deferred, hints);
+  hipLaunchKernelGGL((hw_dg_kernel<K, PRUNE, T>), dim3(grid), dim3(256), dlds, st, *a, hmax, deferred, hints);
   return hipGetLastError();
 }
 
@@ -2659,9 +2697,10 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
 // followed by float [max_split * 2 * 2 * CAND_FLOATS] candidates; the counters must be zero
 // on entry (they are left zero).  `grid_quads`: G % 4 == 0 and grid rows 4q .. 4q + 3 carry
 // the same (alpha, beta), bit for bit (the caller checks it once per grid): hw_d_kernel then
-// walks season 1 once per (alpha, beta) (see QuadQueue).
-extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
-                                 int slots, hipStream_t st, int grid_quads) {
+// walks season 1 once per (alpha, beta) (see QuadQueue).  `fp32`: the ring's element type
+// (0: bf16, else fp32).
+extern "C" int fm_hw_d_fit_split_dt(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
+                                    int slots, hipStream_t st, int grid_quads, int fp32) {
   const int K = a->K;
   if (!d_supported_k(K) || a->seg != 32 * K || a->m != a->seg || a->Tp % a->seg != 0 || a->Tp / a->seg < 2 ||
       a->Tp / a->seg > D_MAXSEG || !a->pair_tab || a->season_out || hmax < 1 || hmax > K || hmax > HALF_HB)
@@ -2671,9 +2710,17 @@ extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, i
     return (int)hipErrorNotSupported;
   if (!deferred) return (int)hipErrorInvalidValue;
   const GridSwitches sw = grid_switches();
-  const auto launch = K == 45 ? (sw.prune ? launch_d_fit<45, true> : launch_d_fit<45, false>)
-                              : (sw.prune ? launch_d_fit<9, true> : launch_d_fit<9, false>);
+  const auto launch =
+      fp32 ? (K == 45 ? (sw.prune ? launch_d_fit<45, true, float> : launch_d_fit<45, false, float>)
+                      : (sw.prune ? launch_d_fit<9, true, float> : launch_d_fit<9, false, float>))
+           : (K == 45 ? (sw.prune ? launch_d_fit<45, true, bf16_t> : launch_d_fit<45, false, bf16_t>)
+                      : (sw.prune ? launch_d_fit<9, true, bf16_t> : launch_d_fit<9, false, bf16_t>));
   return (int)launch(a, hmax, deferred, split_ws, max_split, slots, sw.hints, (sw.share && grid_quads) ? 1 : 0, st);
+}
+
+extern "C" int fm_hw_d_fit_split(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
+                                 int slots, hipStream_t st, int grid_quads) {
+  return fm_hw_d_fit_split_dt(a, hmax, deferred, split_ws, max_split, slots, st, grid_quads, 0);
 }
 
 extern "C" int fm_hw_d_fit(const SmoothArgs* a, int hmax, int* deferred, hipStream_t st) {

@@ -419,6 +419,11 @@ def smoothing_fit(hist: torch.Tensor, head: int, length: int, mode: int, m: int,
     at run time (HIP-graph replays); only the two-series-per-wave HW variants
     (4/5) support it — other paths raise.
 
+    Ring dtype: variant 5 (the 60 s and 300 s steps, quad and pair kernels) fits
+    float32 and bfloat16 rings alike — only its staging reads the ring; variant 4
+    (``FOREMAST_HW_VARIANT=4``) keeps a bf16 image and takes bfloat16 rings only,
+    a float32 ring there falls to variant 3.
+
     ``defer_detect``: on the variant 4/5 path the fit skips the band/verdict
     epilogue and stores what it needs (``season_hb``, ``nvalid``); call
     :func:`hw_detect_deferred` afterwards (``det.differs`` is read only then, so
@@ -452,18 +457,19 @@ def smoothing_fit(hist: torch.Tensor, head: int, length: int, mode: int, m: int,
                            head_dev=head_dev, defer=defer_detect, detect_after=detect_after)
     if variant in (4, 5):
         hmax = det.max_horizon
-        if (variant == 5 and mode == MODE_HW and bf16 and mm % 16 == 0 and mm // 16 in QUAD_K
+        if (variant == 5 and mode == MODE_HW and mm % 16 == 0 and mm // 16 in QUAD_K
                 and not want_season and K is None and hmax is not None and 1 <= hmax <= min(mm // 16, HALF_HB)
                 and os.environ.get("FOREMAST_HW_QUAD", "1") != "0"
                 and lib.fm_hw_q_lds_bytes(Tp, mm, mm // 16) <= D_LDS_LIMIT):
             return _hw_half_fit(lib, hist, head, length, mm, grid, det, Tp, pad, hmax, out, residual=True,
                                 head_dev=head_dev, defer=defer_detect, quad=True)
-        if (mode == MODE_HW and bf16 and mm % 32 == 0 and mm // 32 in HALF_K and not want_season
+        if (mode == MODE_HW and mm % 32 == 0 and mm // 32 in HALF_K and not want_season
                 and hmax is not None and 1 <= hmax <= min(mm // 32, HALF_HB) and K is None):
             if variant == 5 and lib.fm_hw_d_lds_bytes(Tp, mm, mm // 32) <= D_LDS_LIMIT:
                 return _hw_half_fit(lib, hist, head, length, mm, grid, det, Tp, pad, hmax, out, residual=True,
                                     head_dev=head_dev, defer=defer_detect)
-            if mm // 32 == 45 and lib.fm_hw_half_lds_bytes(Tp, mm, mm // 32) <= LDS_LIMIT:
+            # variant 4 keeps a bf16 image of the ring: bf16 rings only
+            if bf16 and mm // 32 == 45 and lib.fm_hw_half_lds_bytes(Tp, mm, mm // 32) <= LDS_LIMIT:
                 return _hw_half_fit(lib, hist, head, length, mm, grid, det, Tp, pad, hmax, out, head_dev=head_dev,
                                     defer=defer_detect)
         variant = 3
@@ -569,10 +575,11 @@ def _hw_half_fit(lib, hist, head, length, m, grid, det, Tp, pad, hmax, out, resi
                  head_dev: Optional[torch.Tensor] = None, defer: bool = False, quad: bool = False):
     """Variants 4/5 of the Holt-Winters fit: two series per wave, season = 32
     lanes x K steps.  Variant 4 (hw_scan.hip ``hw_half_kernel``) walks the
-    seasonal state over a bf16 image; variant 5 (``residual``, ``hw_d_kernel``)
-    walks D = y - s over an fp32 image of season differences (fewer ops per
-    step, at most 7 seasons).  Pairs with gaps past season 0 go to the general
-    kernel in both."""
+    seasonal state over a bf16 image (bfloat16 rings only); variant 5
+    (``residual``, ``hw_d_kernel``; ``quad``: ``hw_q_kernel``) walks D = y - s
+    over an fp32 image of season differences (fewer ops per step, at most 7
+    seasons) staged from a bfloat16 or a float32 ring.  Pairs with gaps past
+    season 0 go to the general kernel in both."""
     dev = hist.device
     N = hist.shape[0]
     k = m // 16 if quad else m // 32
@@ -592,23 +599,26 @@ def _hw_half_fit(lib, hist, head, length, m, grid, det, Tp, pad, hmax, out, resi
     ws = _half_workspace(dev, N)
     global last_hw_variant, last_detect_deferred
     last_detect_deferred = defer
+    fp32 = int(hist.dtype == torch.float32)
+    _need(residual or not fp32, "HW variant 4 needs a bfloat16 ring")
     if quad:
         # four series per wave at K = m / 16; gapped pairs go to the 32-lane kernel at m / 32
-        rc = lib.fm_hw_q_fit(a, nat.ptr(pair_table(grid, m // 32)), int(hmax), nat.ptr(ws), nat.stream_handle(dev))
+        rc = lib.fm_hw_q_fit_dt(a, nat.ptr(pair_table(grid, m // 32)), int(hmax), nat.ptr(ws),
+                                nat.stream_handle(dev), fp32)
         if rc != 0:
             ws.zero_()
-        nat.check(rc, "fm_hw_q_fit")
+        nat.check(rc, "fm_hw_q_fit_dt")
         last_hw_variant = 5
         return out
     if residual:
         sws, slots = _split_workspace(dev)
         if os.environ.get("FOREMAST_HW_SPLIT", "1") == "0":
             slots = 0  # whole pairs only
-        rc = lib.fm_hw_d_fit_split(a, int(hmax), nat.ptr(ws), nat.ptr(sws), SPLIT_MAX, slots,
-                                   nat.stream_handle(dev), int(grid_has_quads(grid)))
+        rc = lib.fm_hw_d_fit_split_dt(a, int(hmax), nat.ptr(ws), nat.ptr(sws), SPLIT_MAX, slots,
+                                      nat.stream_handle(dev), int(grid_has_quads(grid)), fp32)
         if rc != 0:
             ws.zero_()  # the general kernel did not run: its self-cleaning reset did not happen
-        nat.check(rc, "fm_hw_d_fit_split")
+        nat.check(rc, "fm_hw_d_fit_split_dt")
         last_hw_variant = 5
         return out
     rc = lib.fm_hw_half_fit(a, int(hmax), nat.ptr(ws), nat.stream_handle(dev))

@@ -35,6 +35,8 @@ ALGORITHMS = (
     "bivariate_normal", "lstm",
 )
 
+RING_DTYPES = ("bf16", "fp32")  # FOREMAST_DTYPE
+
 PAIRWISE_ALGORITHMS = ("ALL", "ANY", "MANN_WHITE", "WILCOXON", "KRUSKAL", "FRIEDMAN", "NONE")
 
 
@@ -113,6 +115,16 @@ class BrainConfig:
                 return th
         return MetricThreshold(self.threshold, self.bound, self.min_lower_bound)
 
+    def ring_dtype(self, device):
+        """Element type of the history rings on ``device`` (FOREMAST_DTYPE): ``bf16`` is
+        bfloat16 on a GPU and float32 on the CPU, ``fp32`` is float32 everywhere
+        (docs/SCORING.md "Ring precision" says when to choose it)."""
+        import torch
+        if self.dtype not in RING_DTYPES:
+            raise ValueError(f"FOREMAST_DTYPE must be one of {RING_DTYPES}, not {self.dtype!r}")
+        gpu = torch.device(device).type == "cuda"
+        return torch.bfloat16 if self.dtype == "bf16" and gpu else torch.float32
+
     @classmethod
     def from_env(cls, env: Optional[Mapping[str, str]] = None) -> "BrainConfig":
         e = dict(os.environ if env is None else env)
@@ -154,7 +166,9 @@ class BrainConfig:
         c.lstm_threshold = f("ML_LSTM_THRESHOLD", c.lstm_threshold)
         c.lstm_level_threshold = f("FOREMAST_LSTM_LEVEL_THRESHOLD", c.lstm_level_threshold)
         c.downstream_algorithm = (e.get("ML_DOWNSTREAM_ALGORITHM") or c.downstream_algorithm).strip().lower()
-        c.dtype = e.get("FOREMAST_DTYPE", c.dtype)
+        c.dtype = (e.get("FOREMAST_DTYPE") or c.dtype).strip().lower()
+        if c.dtype not in RING_DTYPES:
+            raise ValueError(f"FOREMAST_DTYPE must be one of {RING_DTYPES}, not {c.dtype!r}")
         c.device = e.get("FOREMAST_DEVICE", c.device)
         c.ring_len = int(f("FOREMAST_RING_LEN", c.ring_len, int))
         c.season = int(f("FOREMAST_SEASON", c.season, int))
