@@ -886,7 +886,10 @@ def setup_node_lstm(args, world, rank, dev):
     t_setup = time.perf_counter()
     env = reference_default_env()
     env.update(ML_ALGORITHM="lstm", ML_LSTM_THRESHOLD=str(args.lstm_threshold),
-               FOREMAST_LSTM_LEVEL_THRESHOLD=str(args.lstm_level_threshold), FOREMAST_LSTM_WINDOW=str(args.lstm_window))
+               FOREMAST_LSTM_LEVEL_THRESHOLD=str(args.lstm_level_threshold), FOREMAST_LSTM_WINDOW=str(args.lstm_window),
+               # the process environment's switch (like the pretrain variables above): 1 measures the
+               # attribution kernels, unset / 0 the plain ones
+               FOREMAST_LSTM_ATTRIBUTION=os.environ.get("FOREMAST_LSTM_ATTRIBUTION", "0"))
     cfg = BrainConfig.from_env(env)
     cfg.ring_len, cfg.season = R, season
     store = MemoryJobStore()
@@ -1031,6 +1034,7 @@ def setup_node_lstm(args, world, rank, dev):
         "history": R,
         "entities": n_jobs,
         "features": F,
+        "lstm_attribution": bool(lstm.shard.attribution),
         "path": "service.register (continuous) -> claim -> resident 7-day history -> per tick: query_range JSON of "
                 "every (app, metric) -> native decode -> ring append -> DP train step -> fused scoring -> verdicts",
         "pretrain_steps": pre, "pretrain_per_tick": per,

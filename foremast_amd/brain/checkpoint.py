@@ -130,6 +130,9 @@ def save_lstm_shard(shard, path: str, extra: Optional[Dict[str, Any]] = None) ->
         tensors["cal"] = shard.cal
     if shard.lvl_sig is not None:
         tensors["lvl_sig"] = shard.lvl_sig
+    if shard.cal_feat is not None:
+        tensors["cal_feat"] = shard.cal_feat
+    tensors["n_feat"] = shard.n_feat
     hidden = int(shard.model.H)
     meta = {"format": FORMAT, "kind": "lstm_shard",
             "args": {"n_series": shard.n, "ring_len": shard.R, "n_features": shard.F, "window": shard.T,
@@ -139,9 +142,10 @@ def save_lstm_shard(shard, path: str, extra: Optional[Dict[str, Any]] = None) ->
                      "dtype": _dtype_name(shard.rings[0].data.dtype), "cal_windows": int(shard.cal_windows),
                      "cal_ewma": float(shard.cal_ewma), "season": int(shard.season),
                      "level_points": int(shard.level_points), "level_cal": int(shard.level_cal),
-                     "level_threshold": shard.level_threshold},
+                     "level_threshold": shard.level_threshold, "attribution": bool(shard.attribution)},
             "param_groups": opt["param_groups"], "trainer_steps": int(shard.trainer.steps),
-            "mu": float(shard.mu), "sigma": float(shard.sigma), "rho": float(shard.rho), "ticks": int(shard.ticks),
+            "mu": float(shard.mu), "sigma": float(shard.sigma), "rho": float(shard.rho), "rho1": float(shard.rho1),
+            "ticks": int(shard.ticks),
             "rings": [[r.head, r.length] for r in shard.rings], "extra": extra or {}}
     _atomic_save(tensors, meta, path)
 
@@ -161,7 +165,8 @@ def load_lstm_shard(path: str, device="cpu"):
                       restat_every=a["restat_every"], dtype=dtype, fused_train=a["fused_train"],
                       cal_windows=int(a.get("cal_windows", 0)), cal_ewma=float(a.get("cal_ewma", 0.0)),
                       season=int(a.get("season", 1440)), level_points=int(a.get("level_points", 8)),
-                      level_cal=int(a.get("level_cal", 64)), level_threshold=a.get("level_threshold", None))
+                      level_cal=int(a.get("level_cal", 64)), level_threshold=a.get("level_threshold", None),
+                      attribution=bool(a.get("attribution", False)))
     for f, ring in enumerate(shard.rings):
         ring._store.copy_(t[f"ring{f}"])
         ring.state = RingState(head=int(meta["rings"][f][0]), length=int(meta["rings"][f][1]))
@@ -180,6 +185,12 @@ def load_lstm_shard(path: str, device="cpu"):
     shard.rho = float(meta.get("rho", 1.0))
     shard.cal = t["cal"].float().contiguous() if "cal" in t else None
     shard.lvl_sig = t["lvl_sig"].float().contiguous() if "lvl_sig" in t else None
+    # snapshots from before the per-feature attribution carry none of these: every feature
+    # of a flagged row is named until the next calibrate()
+    shard.rho1 = float(meta.get("rho1", 1.0))
+    shard.cal_feat = t["cal_feat"].float().contiguous() if "cal_feat" in t else None
+    if "n_feat" in t:
+        shard.n_feat = t["n_feat"].to(torch.int32).contiguous()
     shard.ticks = int(meta["ticks"])
     shard.packed = None  # repacked for the fused scorer on the next score
     shard.checkpoint_extra = meta.get("extra", {})

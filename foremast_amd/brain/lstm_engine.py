@@ -43,6 +43,16 @@ divided by that statistic's own spread — calibrated on the series' history as
 the RMS of the statistic at ``level_cal`` earlier offsets (:meth:`calibrate`).  A window is anomalous when the AE z-score OR any
 feature's ``|level z|`` exceeds its threshold (``level_threshold``; the
 epilogue also keeps such windows out of the calibration refresh).
+
+Attribution (``attribution=True``, off by default): the verdict is one per entity,
+and a job document has to say WHICH metric broke.  :meth:`calibrate` also keeps each
+feature's healthy error level ``mu_f`` (``cal_feat [n, F, 2]``, from the same windows;
+the relative spread ``rho1`` pooled over (series, feature)), and the scoring kernel's
+epilogue names the features whose own ``z_f = (err_f - mu_f) / (rho1 mu_f)`` exceeds
+the entity's threshold or whose level z exceeds ``level_threshold``
+(:func:`~foremast_amd.models.lstm_ae.attribute`; ``out["blame"]``, bit f = feature f).
+A flagged entity none of whose features does names the largest ``z_f``.  Every other
+output is the same with and without it.
 """
 
 from __future__ import annotations
@@ -54,7 +64,7 @@ import torch
 import torch.distributed as dist
 
 from ..ingest.ringbuffer import HistoryRing
-from ..models.lstm_ae import LSTMAutoencoder
+from ..models.lstm_ae import LSTMAutoencoder, attribute
 from ..parallel import comm
 from ..parallel.dp import DPTrainer
 
@@ -68,7 +78,8 @@ class LstmShard:
                  threshold: float = 4.0, train_batch: int = 4096, lr: float = 1e-3, restat_every: int = 16,
                  seed: int = 0, dtype=torch.bfloat16, fused_train: bool = True, cal_windows: int = 16,
                  cal_ewma: float = 1.0 / 32, dp_overlap: bool = True, season: int = 1440,
-                 level_points: int = 8, level_threshold: Optional[float] = 5.5, level_cal: int = 64) -> None:
+                 level_points: int = 8, level_threshold: Optional[float] = 5.5, level_cal: int = 64,
+                 attribution: bool = False) -> None:
         self.n, self.R, self.F, self.T = n_series, ring_len, n_features, window
         self.device = torch.device(device)
         self.gpu = self.device.type == "cuda"
@@ -101,6 +112,12 @@ class LstmShard:
         self.cal_windows, self.cal_ewma = cal_windows, cal_ewma
         self.cal: Optional[torch.Tensor] = None  # [n, 2] (mu_i, 1 / (rho * mu_i)) after calibrate()
         self.rho = 1.0
+        # per-feature attribution of the verdict: [n, F, 2] (mu_f, 1 / (rho1 * mu_f)) after
+        # calibrate(); n_feat: real features per row (the rest are zero padding, never named)
+        self.attribution = bool(attribution)
+        self.cal_feat: Optional[torch.Tensor] = None
+        self.rho1 = 1.0
+        self.n_feat = torch.full((n_series,), n_features, dtype=torch.int32, device=self.device)
         if level_points != 8:
             raise ValueError("level_points: the level kernel averages the newest 8 points")
         self.season, self.level_points, self.level_cal = int(season), int(level_points), int(level_cal)
@@ -153,6 +170,9 @@ class LstmShard:
         self.app_id = ext(self.app_id, 0)
         if self.cal is not None:
             self.cal = ext(self.cal, 1.0).contiguous()
+        if self.cal_feat is not None:
+            self.cal_feat = ext(self.cal_feat, 1.0).contiguous()
+        self.n_feat = ext(self.n_feat, self.F)
         if self.lvl_sig is not None:  # rows not calibrated yet carry no level term (z = 0)
             self.lvl_sig = ext(self.lvl_sig, float("inf")).contiguous()
         self.n = capacity
@@ -310,7 +330,7 @@ class LstmShard:
         if self.live is not None and self.live.numel() == 0:  # nothing live here: join the reductions
             e = torch.zeros(0, dtype=torch.float64, device=self.device)
         else:
-            e = self._calib_errors(self._sample_ring(n) if self.gpu else None, n)
+            e = self._calib_errors(self._sample_ring(n) if self.gpu else None, n)[0]
         e = e[torch.isfinite(e)]
         mom = torch.stack([e.sum(), (e * e).sum(), torch.tensor(float(e.numel()), dtype=torch.float64,
                                                                 device=e.device)])
@@ -320,7 +340,7 @@ class LstmShard:
             self.mu = s1 / cnt
             self.sigma = max(s2 / cnt - self.mu * self.mu, 0.0) ** 0.5 + 1e-12
         if self.cal_windows <= 0:
-            self.cal = None
+            self.cal = self.cal_feat = None
             return
         K, L, R = self.cal_windows, self.rings[0].length, self.rings[0].R
         span = max(L - self.T, 1)
@@ -332,28 +352,30 @@ class LstmShard:
             si = sel.to(torch.int32).repeat(K)
             st = torch.tensor([(head + o) % R for o in offs], dtype=torch.int32,
                               device=self.device).repeat_interleave(nr)
-            ek = self._calib_errors(self._ring_src(si, st), K * nr).view(K, nr)
+            ek, ekf = self._calib_errors(self._ring_src(si, st), K * nr)
+            ek = ek.view(K, nr)
         else:
-            ek = torch.stack([self._calib_errors(self._gather(sel, torch.full_like(
-                sel, L - self.T - o)), nr) for o in offs])
-        ek = torch.where(torch.isfinite(ek), ek, torch.nan)
-        srt = ek.sort(0).values  # NaN last
-        ok = torch.isfinite(srt)
-        cnt_i = ok.sum(0)
-        keep = ok & (torch.arange(K, device=ek.device)[:, None] < (cnt_i - 1).clamp(min=1)[None, :])
-        mu_i = torch.where(keep, srt, 0.0).sum(0) / keep.sum(0).clamp(min=1)
+            pairs = [self._calib_errors(self._gather(sel, torch.full_like(sel, L - self.T - o)), nr) for o in offs]
+            ek = torch.stack([p[0] for p in pairs])
+            ekf = torch.stack([p[1] for p in pairs]) if self.attribution else None
         floor = max(self.mu * 1e-3, 1e-12)
-        mu_i = torch.where(cnt_i > 0, mu_i, self.mu).clamp(min=floor)
-        r = ek / mu_i[None, :] - 1.0
-        r = r[torch.isfinite(r)]
-        mom = torch.stack([r.sum(), (r * r).sum(), torch.tensor(float(r.numel()), dtype=torch.float64,
-                                                                device=r.device)])
-        self._all_reduce(mom)
-        r1, r2, rc = mom.tolist()
-        m1 = r1 / max(rc, 1.0)
-        if rc > 0:
-            self.rho = max((max(r2 / max(rc, 1.0) - m1 * m1, 0.0)) ** 0.5, 1e-6)
+        mu_i, rho = self._level_and_spread(ek, floor)
+        if rho is not None:
+            self.rho = rho
         new = torch.stack([mu_i, 1.0 / (self.rho * mu_i)], 1).float()
+        if self.attribution:
+            # the same windows per feature: mu_f, and rho1 pooled over (series, real feature)
+            real = torch.arange(self.F, device=self.device)[None, :] < self.n_feat[sel][:, None]
+            mu_f, rho1 = self._level_and_spread(ekf.view(K, nr, self.F), floor, pool=real)
+            if rho1 is not None:
+                self.rho1 = rho1
+            newf = torch.stack([mu_f, 1.0 / (self.rho1 * mu_f)], 2).float()
+            if rows is None or self.cal_feat is None:
+                fullf = torch.ones((self.n, self.F, 2), dtype=torch.float32, device=self.device)
+                fullf[sel] = newf
+                self.cal_feat = fullf.contiguous()
+            else:
+                self.cal_feat[sel] = newf
         if rows is None or self.cal is None:
             full = torch.ones((self.n, 2), dtype=torch.float32, device=self.device)
             full[sel] = new
@@ -361,6 +383,33 @@ class LstmShard:
         else:
             self.cal[sel] = new
         self.calibrate_level(rows)
+
+    def _level_and_spread(self, ek: torch.Tensor, floor: float, pool: Optional[torch.Tensor] = None):
+        """Healthy level and pooled relative spread of calibration errors ``ek [K, ...]``
+        (K windows of every series, or of every (series, feature)): the level is the mean
+        over K without the largest value (so one unusual day does not inflate it; NaN
+        windows ignored, no window: the global ``mu``), floored; the spread is the standard
+        deviation of ``ek / level - 1`` over every window (``pool``: only where it is set),
+        its moments all-reduced across the ranks (None: no window anywhere)."""
+        K = ek.shape[0]
+        ek = torch.where(torch.isfinite(ek), ek, torch.nan)
+        srt = ek.sort(0).values  # NaN last
+        ok = torch.isfinite(srt)
+        cnt_i = ok.sum(0)
+        k_idx = torch.arange(K, device=ek.device).view((K,) + (1,) * (ek.dim() - 1))
+        keep = ok & (k_idx < (cnt_i - 1).clamp(min=1)[None])
+        mu_i = torch.where(keep, srt, 0.0).sum(0) / keep.sum(0).clamp(min=1)
+        mu_i = torch.where(cnt_i > 0, mu_i, self.mu).clamp(min=floor)
+        r = ek / mu_i[None] - 1.0
+        sel = torch.isfinite(r) if pool is None else torch.isfinite(r) & pool[None]
+        r = r[sel]
+        mom = torch.stack([r.sum(), (r * r).sum(), torch.tensor(float(r.numel()), dtype=torch.float64,
+                                                                device=r.device)])
+        self._all_reduce(mom)
+        r1, r2, rc = mom.tolist()
+        m1 = r1 / max(rc, 1.0)
+        rho = max((max(r2 / max(rc, 1.0) - m1 * m1, 0.0)) ** 0.5, 1e-6) if rc > 0 else None
+        return mu_i, rho
 
     # ------------------------------------------------------------------ level term
     @property
@@ -462,17 +511,29 @@ class LstmShard:
         st = self._level_stat_cpu(0)
         return torch.where(torch.isfinite(st) & (self.lvl_sig > 0), st / self.lvl_sig, 0.0)
 
-    def _calib_errors(self, src, n: int) -> torch.Tensor:
+    def _calib_errors(self, src, n: int):
         """Reconstruction errors (float64) of ``src``'s windows: a kernel
         ``RingSource`` on the GPU, a ``[B, T, F]`` window tensor on the CPU
-        (``None``: ``n`` random history windows)."""
+        (``None``: ``n`` random history windows).  Returns ``(err [B], err_feat [B, F])``,
+        the per-feature errors only with ``attribution`` (else None)."""
         if self.gpu:
             from ..ops import lstm as L
             self._pack_scoring()
-            return L.lstm_score(self.packed, None, 0.0, 1.0, thr_default=float("inf"), ring=src,
-                                T=self.T)["err"].double()
+            attr = None
+            if self.attribution:  # the attribution kernel against a neutral calibration: err_feat is what is read
+                B = src.win_series.shape[0] if src.win_series is not None else self.n
+                attr = {"cal": torch.ones((B, self.F, 2), dtype=torch.float32, device=self.device),
+                        "blame": torch.empty(B, dtype=torch.int32, device=self.device),
+                        "err_feat": torch.empty((B, self.F), dtype=torch.float32, device=self.device)}
+            err = L.lstm_score(self.packed, None, 0.0, 1.0, thr_default=float("inf"), ring=src, T=self.T,
+                               attr=attr)["err"].double()
+            return err, (attr["err_feat"].double() if attr is not None else None)
         with torch.no_grad():
-            return self.model.recon_error(self._sample(n) if src is None else src).double()
+            x = self._sample(n) if src is None else src
+            if not self.attribution:
+                return self.model.recon_error(x).double(), None
+            d2 = (self.model(x) - x) ** 2
+            return d2.mean(dim=(1, 2)).double(), d2.mean(dim=1).double()
 
     @staticmethod
     def _all_reduce(t: torch.Tensor) -> None:
@@ -503,11 +564,25 @@ class LstmShard:
         if not zeroed:
             self.app_stats.zero_()
         ring = ring if ring is not None else self._ring_src()
+        attr = None
+        if self.attribution:
+            if self.out.get("blame") is None:
+                self.out["blame"] = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+            if self.cal is not None and self.cal_feat is not None:
+                attr = {"cal": self.cal_feat, "blame": self.out["blame"], "n_feat": self.n_feat}
         self.out = L.lstm_score(self.packed, None, self.mu, self.sigma, thr_default=self.threshold,
                                 app_id=self.app_id, app_stats=self.app_stats, out=self.out,
                                 ring=ring, T=self.T, cal=self.cal, cal_ewma=self.cal_ewma,
-                                thr_level=float(self.level_threshold or float("inf")), level=self._level_args(ring))
+                                thr_level=float(self.level_threshold or float("inf")), level=self._level_args(ring),
+                                attr=attr)
+        if self.attribution and attr is None:  # no per-feature calibration yet: every real feature
+            self.out["blame"].copy_(self._blame_all(self.out["verdict"]))
         return self.out
+
+    def _blame_all(self, verdict: torch.Tensor) -> torch.Tensor:
+        """The mask naming every real feature of the flagged rows."""
+        every = torch.bitwise_left_shift(torch.ones_like(self.n_feat), self.n_feat) - 1
+        return torch.where(verdict != 0, every, torch.zeros_like(every))
 
     def tick(self, newx: torch.Tensor, train: bool = True, overlap: bool = True) -> Dict[str, torch.Tensor]:
         """Ingest + (optional) DP training step + scoring of every series.
@@ -610,7 +685,8 @@ class LstmShard:
         key = (newx.data_ptr(), tuple(newx.shape), tuple(r.data.data_ptr() for r in self.rings), live,
                None if self.lvl_sig is None else self.lvl_sig.data_ptr(), self.level_threshold,
                None if self.cal is None else self.cal.data_ptr(), self.cal_ewma, self.mu, self.sigma,
-               self.threshold, self.app_stats.data_ptr(), self.app_id.data_ptr(), id(self.packed))
+               self.threshold, self.app_stats.data_ptr(), self.app_id.data_ptr(), id(self.packed),
+               self.attribution, None if self.cal_feat is None else self.cal_feat.data_ptr(), self.n_feat.data_ptr())
         if self._graph is not None and key == self._graph_key:
             self._graph.replay()
             self.graph_replays += 1
@@ -641,8 +717,13 @@ class LstmShard:
             return self._score_packed()
         x = self._gather(self._all, self._zero_off)
         self.app_stats.zero_()
+        ef = None
         with torch.no_grad():
-            err = self.model.recon_error(x)
+            if self.attribution:
+                d2 = (self.model(x) - x) ** 2
+                err, ef = d2.mean(dim=(1, 2)), d2.mean(dim=1)
+            else:
+                err = self.model.recon_error(x)
         z = (err - self.mu) / max(self.sigma, 1e-12)
         zs = None
         if self.cal is not None:
@@ -653,8 +734,20 @@ class LstmShard:
         if zl is not None:  # same level term as the kernel epilogue
             v = v | (zl.abs().amax(1) > float(self.level_threshold))
         v = v.to(torch.int8)
+        blame = None
+        if self.attribution:  # same rule as the kernel epilogue
+            if self.cal is not None and self.cal_feat is not None:
+                blame = attribute(ef, self.cal_feat, float(self.threshold), zl,
+                                  float(self.level_threshold or float("inf")), v, self.n_feat)
+            else:
+                blame = self._blame_all(v)
         if self.cal is not None and self.cal_ewma > 0:  # same update (and gate) as the kernel epilogue
             upd = (v == 0) & torch.isfinite(err) & (zs <= CAL_GATE)
+            if self.attribution and self.cal_feat is not None:
+                mu_f = self.cal_feat[..., 0]
+                nmu_f = torch.where(upd[:, None], mu_f + self.cal_ewma * (ef - mu_f), mu_f)
+                self.cal_feat[..., 1] *= mu_f / nmu_f
+                self.cal_feat[..., 0] = nmu_f
             nmu = self.cal[:, 0] + self.cal_ewma * (err - self.cal[:, 0])
             nmu = torch.where(upd, nmu, self.cal[:, 0])
             self.cal[:, 1] *= self.cal[:, 0] / nmu
@@ -664,4 +757,6 @@ class LstmShard:
         self.app_stats.index_put_((ids, torch.ones_like(ids)), torch.ones_like(v, dtype=torch.int32),
                                   accumulate=True)
         self.out = {"err": err, "zscore": z, "verdict": v}
+        if blame is not None:
+            self.out["blame"] = blame
         return self.out

@@ -25,8 +25,10 @@ LSTM-autoencoder per node, trained data-parallel across the ranks
 * the fused MFMA kernel scores every entity's newest window (bf16; fp8 e4m3
   with ``FOREMAST_LSTM_FP8=1``) → per-entity z-score against its calibrated
   error level → verdict; an anomalous entity finishes its job
-  ``completed_unhealth`` naming every metric with its newest point, past
-  ``endTime`` the job finishes ``completed_health``.
+  ``completed_unhealth`` naming every metric with its newest point — with
+  ``FOREMAST_LSTM_ATTRIBUTION=1`` only the metrics the kernel's epilogue blames the
+  verdict on (:func:`~foremast_amd.models.lstm_ae.attribute`) — past ``endTime`` the
+  job finishes ``completed_health``.
 """
 
 from __future__ import annotations
@@ -137,7 +139,8 @@ class LstmMonitor:
                                dtype=torch.bfloat16 if self.gpu else torch.float32, dp_overlap=False,
                                restat_every=1 << 30, season=self.cfg.season,
                                level_threshold=(self.cfg.lstm_level_threshold
-                                                if self.cfg.lstm_level_threshold > 0 else None))
+                                                if self.cfg.lstm_level_threshold > 0 else None),
+                               attribution=self.cfg.lstm_attribution)
         for ring in self.shard.rings:
             ring.state.head, ring.state.length = 0, R
         self.shard.live = torch.zeros(0, dtype=torch.int64, device=self.device)
@@ -178,7 +181,8 @@ class LstmMonitor:
         self.sync_history = True     # False: another monitor drives the shared history
         self._feed: Optional[Tuple[List[str], np.ndarray]] = None
         self._row_of: Dict[str, int] = {}   # admitted entity -> row (C-level lookups of a fed batch)
-        self.hits: Dict[str, Tuple[float, np.ndarray]] = {}
+        # flagged external entities: (minute, newest values, blamed-feature mask; -1: every feature)
+        self.hits: Dict[str, Tuple[float, np.ndarray, int]] = {}
 
     # ------------------------------------------------------------------ membership
     def is_mine(self, d) -> bool:
@@ -403,6 +407,7 @@ class LstmMonitor:
         fr_t = torch.from_numpy(fr).to(self.device)
         self.feat_rows[idx] = fr_t
         self.padded[idx] = fr_t < 0
+        self.shard.n_feat[idx] = torch.from_numpy(lens_r.astype(np.int32)).to(self.device)  # padding is never blamed
         # the week of each feature, from the resident ring (logical order, ending at t_last)
         ring = hist.ring
         cols = (torch.arange(hist.R, device=self.device) + ring.head) % hist.R
@@ -532,6 +537,8 @@ class LstmMonitor:
         hit = (v == 1) & cal
         rows = np.nonzero(hit | (cal & (self._row_end[:n] <= now)))[0]
         newest = self._newest() if hit.any() else None
+        # bit f of a flagged row: its feature f is named (attribution off: every feature)
+        blame = out["blame"].cpu().numpy() if self.cfg.lstm_attribution and hit.any() else None
         items = []
         for row in rows.tolist():
             jid = self.row_job[row]
@@ -540,11 +547,14 @@ class LstmMonitor:
                 continue
             if e.external:  # the rollout engine owns the job: it reads the verdict back
                 if v[e.row] == 1:
-                    self.hits[jid] = (self.history.t_last, newest[e.row])
+                    self.hits[jid] = (self.history.t_last, newest[e.row], -1 if blame is None else int(blame[e.row]))
                 continue
             if v[e.row] == 1:
                 nv = newest[e.row].tolist()
                 aliases = [alias for alias, _k in e.feats]
+                if blame is not None:
+                    named = [(a, x) for f, (a, x) in enumerate(zip(aliases, nv)) if (int(blame[e.row]) >> f) & 1]
+                    aliases, nv = [a for a, _ in named], [x for _, x in named]
                 items.append((jid, {"status": r.ST_COMPLETED_UNHEALTH, "claimed_by": "", "modified_ts": now,
                                     "reason": "anomaly detected in " + ",".join(sorted(set(aliases))) + " (lstm)",
                                     "anomalyInfo": anomaly_info(self.history.t_last, dict(zip(aliases, nv)).items()),

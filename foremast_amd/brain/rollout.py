@@ -1578,10 +1578,14 @@ class RolloutMonitor:
             p = jplan[j]
             anomaly = {}
             hit = lstm_hits.get(p.doc_id)
-            if hit is not None:  # the joint LSTM flags every metric at the scored minute (worker: _score_lstm)
-                t_hit, vals_hit = hit
+            if hit is not None:
+                # the joint LSTM flags every metric at the scored minute (worker: _score_lstm); with
+                # FOREMAST_LSTM_ATTRIBUTION=1 only the features its verdict is blamed on (mask bit f)
+                t_hit, vals_hit, mask = hit
                 al = [p.cols.alias[p.s0 + k] for k in range(p.n)]
                 for f, k in enumerate(sorted(range(p.n), key=al.__getitem__)[:len(vals_hit)]):
+                    if not (mask >> f) & 1:
+                        continue
                     anomaly[al[k]] = {"tags": "", "values": [float(t_hit), float(vals_hit[f])]}
                     self.last_anom[p.rows[k]] = float(t_hit)
                 finish[p.doc_id] = (r.ST_COMPLETED_UNHEALTH, "anomaly detected in " + ",".join(sorted(anomaly)),

@@ -119,6 +119,8 @@ def brain(gpus: int = 8) -> List[Dict[str, Any]]:
     env = [{"name": k, "value": v} for k, v in reference_default_env().items()]
     env += [{"name": "ES_ENDPOINT", "value": ES_URL}, {"name": "HSA_ENABLE_IPC_MODE_LEGACY", "value": "0"},
             {"name": "FOREMAST_DTYPE", "value": "bf16"},
+            # 1: a job the joint LSTM flags names only the metrics its verdict is blamed on
+            {"name": "FOREMAST_LSTM_ATTRIBUTION", "value": "0"},
             # resident engines: continuous (streaming) + canary / rollingUpdate (rollout) jobs on the GPUs
             {"name": "FOREMAST_STREAMING", "value": "1"}, {"name": "FOREMAST_ROLLOUT", "value": "1"},
             # "reference": the reference brain's per-point thresholds (no window correction, one point

@@ -70,6 +70,48 @@ class LSTMAutoencoder(nn.Module):
         y = self.forward(x)
         return ((y - x) ** 2).mean(dim=(1, 2))
 
+    def recon_error_features(self, x: torch.Tensor) -> torch.Tensor:
+        """Per-feature reconstruction error ``[N, F]``: ``mean_t (y_tf - x_tf)^2``
+        (its mean over the features is :meth:`recon_error`)."""
+        y = self.forward(x)
+        return ((y - x) ** 2).mean(dim=1)
+
+
+def attribute(err_feat: torch.Tensor, cal_feat: torch.Tensor, thr, zlvl: Optional[torch.Tensor] = None,
+              thr_level: float = float("inf"), verdict: Optional[torch.Tensor] = None,
+              n_feat: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Which features a joint verdict is blamed on: int32 ``[N]``, bit f = feature f
+    (the reference semantics of the fused kernel's attribution epilogue).
+
+    ``cal_feat [N, F, 2]`` holds each feature's healthy error level and inverse spread
+    ``(mu_f, 1 / (rho1 mu_f))``; ``zf = (err_f - mu_f) inv_f``.  Bit f is set when
+    ``zf > thr`` (``thr``: the entity's own verdict threshold, a scalar or ``[N]``) or
+    ``|zlvl_f| > thr_level``.  A row with ``verdict == 1`` and no bit set names the
+    feature of the largest ``zf`` (ties: the lowest f; a NaN ``zf`` counts as -inf); a
+    row with ``verdict == 0`` names nothing.  Features ``f >= n_feat[n]`` (the
+    zero-padded features of a job with fewer metrics) are never named."""
+    N, F = err_feat.shape
+    dev = err_feat.device
+    zf = (err_feat.float() - cal_feat[..., 0].float()) * cal_feat[..., 1].float()
+    thr_t = torch.as_tensor(thr, dtype=torch.float32, device=dev).expand(N)
+    real = torch.ones((N, F), dtype=torch.bool, device=dev)
+    if n_feat is not None:
+        real = torch.arange(F, device=dev)[None, :] < n_feat.to(dev)[:, None]
+    hit = zf > thr_t[:, None]
+    if zlvl is not None:
+        hit = hit | (zlvl.float().abs() > float(thr_level))
+    hit = hit & real
+    bits = (1 << torch.arange(F, device=dev, dtype=torch.int64))[None, :]
+    mask = (hit.to(torch.int64) * bits).sum(1)
+    # fallback: the largest zf among the real features (argmax returns the first maximum)
+    zr = torch.where(torch.isnan(zf) | ~real, torch.full_like(zf, float("-inf")), zf)
+    best = zr.argmax(1) if F > 0 else torch.zeros(N, dtype=torch.int64, device=dev)
+    has_real = real.any(1)
+    mask = torch.where((mask == 0) & has_real, 1 << best, mask)
+    if verdict is not None:
+        mask = torch.where(verdict.to(dev) != 0, mask, torch.zeros_like(mask))
+    return mask.to(torch.int32)
+
 
 @dataclass
 class Calibration:

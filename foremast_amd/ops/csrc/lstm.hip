@@ -60,6 +60,13 @@ struct LstmArgs {
   int lvl_newest;          // newest column (an offset from src.head_dev when that is set)
   int lvl_avail;           // valid samples in the rings
   float* lvl_out;          // optional [N, F] level z written out, or null
+  // per-feature attribution of the verdict (blame != null selects the ATTR kernels): the
+  // reference semantics are models/lstm_ae.py attribute()
+  float* cal_feat;         // [N, F, 2] per-feature (mu_f, 1/sigma_f) of the reconstruction error; tracks like cal
+  float* err_feat;         // [N, F] per-feature error mean_t (y - x)^2, or null
+  float* zfeat;            // [N, F] per-feature z against cal_feat, or null
+  int* blame;              // [N] bit f: feature f is named by the verdict (0: healthy row)
+  const int* n_feat;       // [N] real features of the row (the rest are zero padding, never named), or null (F)
 };
 
 // Level term of the LSTM-AE verdict (lstm_level_kernel): the autoencoder scores the SHAPE
@@ -152,10 +159,12 @@ __device__ __forceinline__ void gates_fp8(const char* wl, int lo, const f8x32& h
 // bf16: v_mfma_f32_32x32x16_bf16, 5 k-steps (h: 4, input + bias: 1).  fp8: CDNA4
 // v_mfma_scale_f32_32x32x64_f8f6f4 on e4m3 with per-(row, 32-k block) E8M0 weight scales
 // (ops/lstm.py pack_fp8), 2 k-steps: the lane's 32 hidden units, then input + bias.
-template <bool FP8, bool ENC>
+// ATTR (decoder): the squared error is also summed per feature into ef (f is a compile-time
+// index of the unrolled read-out loop, so ef stays in registers); errsum is summed as without it.
+template <bool FP8, bool ENC, bool ATTR = false>
 __device__ __forceinline__ void run_phase(const LstmArgs& a, const void* wlds_v, const float* wout_lds,
                                           long long series, bool valid, int hh, float (&hreg)[32],
-                                          float (&creg)[32], float& errsum) {
+                                          float (&creg)[32], float& errsum, float (&ef)[7]) {
   const int lane = lane_id();
   const XPos xp = make_xpos(a.x, a.src, valid ? series : 0, a.T, a.F);  // tail lanes never index past N
   int4 sc = make_int4(0, 0, 0, 0);
@@ -247,7 +256,14 @@ __device__ __forceinline__ void run_phase(const LstmArgs& a, const void* wlds_v,
         const float y = p + a.b_out[f];
         if (valid && hh == 0) {
           const float d = y - load_x(a.src, xp, t, f, a.F);
-          errsum += d * d;
+          if constexpr (ATTR) {
+            // both sums as explicit fmas: the plain kernel's `errsum += d * d` contracts to one,
+            // and a d * d shared by two sums would not (err must not depend on ATTR)
+            errsum = __builtin_fmaf(d, d, errsum);
+            ef[f] = __builtin_fmaf(d, d, ef[f]);
+          } else {
+            errsum += d * d;
+          }
           if (a.recon) a.recon[(series * a.T + t) * a.F + f] = y;
         }
       }
@@ -257,9 +273,11 @@ __device__ __forceinline__ void run_phase(const LstmArgs& a, const void* wlds_v,
 
 // Level z of series n (same statistic as lstm_level_kernel): the two lanes of the series split
 // the days (lane half hh: days hh, hh + 2, hh + 4, hh + 6), exchange their day means, and both
-// fit the least squares over days 1..D.  Returns max_f |z_f|.  Every lane calls it (the
-// exchange is a cross-half shuffle); rows past N compute on row 0 and write nothing.
-__device__ __forceinline__ float fused_level_z(const LstmArgs& a, long long n, bool valid, int hh) {
+// fit the least squares over days 1..D.  Returns max_f |z_f|; ATTR: lmask also gets bit f of
+// every feature with |z_f| > thr_level.  Every lane calls it (the exchange is a cross-half
+// shuffle); rows past N compute on row 0 and write nothing.
+template <bool ATTR>
+__device__ __forceinline__ float fused_level_z(const LstmArgs& a, long long n, bool valid, int hh, int& lmask) {
   const LstmRingSrc& s = a.src;
   const int R = s.ring_len, m = a.lvl_m, E = a.lvl_E, W = LVL_L + 2 * E;
   const int newest = s.head_dev ? (s.head_dev[0] + a.lvl_newest) % R : a.lvl_newest;
@@ -323,11 +341,12 @@ __device__ __forceinline__ float fused_level_z(const LstmArgs& a, long long n, b
     const float z = (st == st && sg > 0.f) ? st / sg : 0.f;
     if (valid && hh == 0 && a.lvl_out) a.lvl_out[n * a.F + f] = z;
     zmax = fmaxf(zmax, fabsf(z));
+    if constexpr (ATTR) lmask |= (fabsf(z) > a.thr_level ? 1 : 0) << f;
   }
   return zmax;
 }
 
-template <bool FP8>
+template <bool FP8, bool ATTR>
 __global__ __launch_bounds__(256, 2) void lstm_ae_kernel(const LstmArgs a) {
   const int w = wave_id(), lane = lane_id();
   const int hh = lane >> 5;
@@ -345,12 +364,14 @@ __global__ __launch_bounds__(256, 2) void lstm_ae_kernel(const LstmArgs a) {
     for (int i = threadIdx.x; i < a.F * H; i += blockDim.x) wout[i] = a.w_out[i];
   }
   __syncthreads();
-  const float zl_fused = a.lvl_sig ? fused_level_z(a, sidx, valid, hh) : 0.f;
+  int lmask = 0;  // ATTR: features whose level z exceeds thr_level
+  const float zl_fused = a.lvl_sig ? fused_level_z<ATTR>(a, sidx, valid, hh, lmask) : 0.f;
   float hreg[32], creg[32];
 #pragma unroll
   for (int i = 0; i < 32; ++i) { hreg[i] = 0.f; creg[i] = 0.f; }
   float errsum = 0.f;
-  run_phase<FP8, true>(a, fm_lstm_smem, wout, sidx, valid, hh, hreg, creg, errsum);
+  float ef[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // ATTR: per-feature sums of d^2
+  run_phase<FP8, true>(a, fm_lstm_smem, wout, sidx, valid, hh, hreg, creg, errsum, ef);
   __syncthreads();
   {
     const uint4* src = (const uint4*)a.w_dec;
@@ -358,7 +379,7 @@ __global__ __launch_bounds__(256, 2) void lstm_ae_kernel(const LstmArgs a) {
     for (int i = threadIdx.x; i < FB / 16; i += blockDim.x) dst[i] = src[i];
   }
   __syncthreads();
-  run_phase<FP8, false>(a, fm_lstm_smem, wout, sidx, valid, hh, hreg, creg, errsum);
+  run_phase<FP8, false, ATTR>(a, fm_lstm_smem, wout, sidx, valid, hh, hreg, creg, errsum, ef);
   if (valid && hh == 0) {
     const float err = errsum / (float)(a.T * a.F);
     a.err[series] = err;
@@ -384,11 +405,46 @@ __global__ __launch_bounds__(256, 2) void lstm_ae_kernel(const LstmArgs a) {
     // level update it: a regression that builds up over several ticks (its
     // first windows still below the verdict threshold) must not be absorbed
     // into the baseline it is judged against.  NaN errors never update it.
-    if (a.cal && a.cal_ewma > 0.f && !v && err == err && zs <= CAL_GATE) {
+    const bool refresh = a.cal && a.cal_ewma > 0.f && !v && err == err && zs <= CAL_GATE;
+    if (refresh) {
       const float mu = a.cal[2 * series];
       const float nmu = mu + a.cal_ewma * (err - mu);
       a.cal[2 * series] = nmu;
       a.cal[2 * series + 1] *= mu / nmu;  // the dispersion is relative to the level
+    }
+    if constexpr (ATTR) {
+      // which features the verdict is blamed on (models/lstm_ae.py attribute()): those whose
+      // own z exceeds the entity's threshold or whose level z exceeds thr_level; a flagged
+      // row none of whose features does names the largest z (ties: the lowest f, NaN: -inf).
+      // Zero-padded features (f >= n_feat) are never named.  The per-feature calibration
+      // tracks healthy errors exactly when the series' own does.
+      int nf = a.F;
+      if (a.n_feat) nf = min(max(a.n_feat[series], 0), a.F);
+      float2* cf = (float2*)a.cal_feat + series * a.F;
+      const float rT = 1.f / (float)a.T;
+      int mask = 0, best = 0;
+      float bestz = -__builtin_inff();
+#pragma unroll
+      for (int f = 0; f < 7; ++f) {
+        if (f >= a.F) break;
+        const float e = ef[f] * rT;
+        const float2 c = cf[f];
+        const float zf = (e - c.x) * c.y;
+        if (a.err_feat) a.err_feat[series * a.F + f] = e;
+        if (a.zfeat) a.zfeat[series * a.F + f] = zf;
+        if (f < nf) {
+          bool lv = (lmask >> f) & 1;
+          if (a.zlvl) lv = lv || fabsf(a.zlvl[series * a.F + f]) > a.thr_level;
+          if (zf > thr || lv) mask |= 1 << f;
+          if (zf > bestz) { bestz = zf; best = f; }
+        }
+        if (refresh) {
+          const float nmu = c.x + a.cal_ewma * (e - c.x);
+          cf[f] = make_float2(nmu, c.y * (c.x / nmu));
+        }
+      }
+      if (mask == 0 && nf > 0) mask = 1 << best;
+      a.blame[series] = v ? mask : 0;
     }
     if (a.app_id) {
       const int app = a.app_id[series];
@@ -495,10 +551,17 @@ extern "C" int fm_lstm_ae(const LstmArgs* a, hipStream_t st) {
     return (int)hipErrorInvalidValue;
   const size_t lds = fm_lstm_lds_bytes(a->F, a->fp8);
   dim3 grid((unsigned)((a->N + 127) / 128)), block(256);
-  if (a->fp8)
-    hipLaunchKernelGGL(lstm_ae_kernel<true>, grid, block, lds, st, *a);
-  else
-    hipLaunchKernelGGL(lstm_ae_kernel<false>, grid, block, lds, st, *a);
+  if (a->blame) {  // attribution: its own instantiations, the plain ones stay as they are
+    if (!a->cal_feat) return (int)hipErrorInvalidValue;
+    if (a->fp8)
+      hipLaunchKernelGGL((lstm_ae_kernel<true, true>), grid, block, lds, st, *a);
+    else
+      hipLaunchKernelGGL((lstm_ae_kernel<false, true>), grid, block, lds, st, *a);
+  } else if (a->fp8) {
+    hipLaunchKernelGGL((lstm_ae_kernel<true, false>), grid, block, lds, st, *a);
+  } else {
+    hipLaunchKernelGGL((lstm_ae_kernel<false, false>), grid, block, lds, st, *a);
+  }
   return (int)hipGetLastError();
 }
 

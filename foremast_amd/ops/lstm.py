@@ -83,6 +83,8 @@ class LstmArgs(C.Structure):
         ("_pad2", C.c_int),
         ("lvl_sig", C.c_void_p), ("lvl_m", C.c_int), ("lvl_E", C.c_int), ("lvl_newest", C.c_int),
         ("lvl_avail", C.c_int), ("lvl_out", C.c_void_p),
+        ("cal_feat", C.c_void_p), ("err_feat", C.c_void_p), ("zfeat", C.c_void_p), ("blame", C.c_void_p),
+        ("n_feat", C.c_void_p),
     ]
 
 
@@ -377,7 +379,8 @@ def lstm_score(p: LstmPacked, x: Optional[torch.Tensor], mu: float = 0.0, sigma:
                out: Optional[Dict[str, torch.Tensor]] = None, ring: Optional[RingSource] = None,
                T: Optional[int] = None, cal: Optional[torch.Tensor] = None,
                cal_ewma: float = 0.0, zlvl: Optional[torch.Tensor] = None,
-               thr_level: float = float("inf"), level: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
+               thr_level: float = float("inf"), level: Optional[Dict] = None,
+               attr: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
     """Score windows ``x [N, T, F]`` — or, with ``ring`` (and ``T``), the last
     ``T`` samples of every ring row (or the ``ring.win_series`` / ``win_start``
     windows) read directly by the kernel.
@@ -392,7 +395,14 @@ def lstm_score(p: LstmPacked, x: Optional[torch.Tensor], mu: float = 0.0, sigma:
     level z itself (:func:`lstm_level`'s statistic) — ``{"sig": [N, F] spread, "m":
     samples per day, "newest": newest column (an offset from ``ring.head_dev`` when set),
     "avail": valid samples, "E": extra points (default :func:`level_extension`),
-    "out": optional [N, F] z}``."""
+    "out": optional [N, F] z}``.
+
+    ``attr``: per-feature attribution of the verdict
+    (:func:`foremast_amd.models.lstm_ae.attribute` in the kernel's epilogue) —
+    ``{"cal": float32 [N, F, 2] per-feature (mu_f, 1/sigma_f), refreshed like ``cal``,
+    "blame": int32 [N] out (bit f: feature f is named), "err_feat" / "zfeat": optional
+    float32 [N, F] outs, "n_feat": optional int32 [N] real features per row}``.  Every
+    other output is bit-identical with and without it."""
     lib = nat.require()
     if ring is None:
         _need(x is not None and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous(),
@@ -451,6 +461,21 @@ def lstm_score(p: LstmPacked, x: Optional[torch.Tensor], mu: float = 0.0, sigma:
         _need(zlvl.shape == (N, F) and zlvl.dtype == torch.float32 and zlvl.is_contiguous() and zlvl.device == dev,
               "zlvl must be float32 [N, F]")
     a.zlvl, a.thr_level = nat.ptr(zlvl), float(thr_level)
+    if attr is not None:
+        unknown = set(attr) - {"cal", "blame", "err_feat", "zfeat", "n_feat"}
+        _need(not unknown, f"unknown attr entries {sorted(unknown)}")
+
+        def ok(t, shape, dtype):
+            return (torch.is_tensor(t) and tuple(t.shape) == shape and t.dtype == dtype and t.is_contiguous()
+                    and t.device == dev)
+        _need(ok(attr.get("cal"), (N, F, 2), torch.float32), "attr cal must be float32 [N, F, 2] (mu_f, 1/sigma_f)")
+        _need(ok(attr.get("blame"), (N,), torch.int32), "attr blame must be int32 [N]")
+        for k in ("err_feat", "zfeat"):
+            _need(attr.get(k) is None or ok(attr[k], (N, F), torch.float32), f"attr {k} must be float32 [N, F]")
+        _need(attr.get("n_feat") is None or ok(attr["n_feat"], (N,), torch.int32), "attr n_feat must be int32 [N]")
+        a.cal_feat, a.blame = attr["cal"].data_ptr(), attr["blame"].data_ptr()
+        a.err_feat, a.zfeat, a.n_feat = nat.ptr(attr.get("err_feat")), nat.ptr(attr.get("zfeat")), \
+            nat.ptr(attr.get("n_feat"))
     nat.check(lib.fm_lstm_ae(C.byref(a), nat.stream_handle(dev)), "fm_lstm_ae")
     return out
 

@@ -68,6 +68,9 @@ class BrainConfig:
     # resident LSTM engine: |z| of the level term (newest points vs their forecast from the
     # earlier days); <= 0 turns it off (FOREMAST_LSTM_LEVEL_THRESHOLD)
     lstm_level_threshold: float = 5.5
+    # resident LSTM engine: a flagged job names only the metrics its verdict is blamed on
+    # (FOREMAST_LSTM_ATTRIBUTION = 0 | 1; docs/SCORING.md "Which metric broke"); off: every metric
+    lstm_attribution: bool = False
     # downstream impact: joint model over each caller's metrics (ML_DOWNSTREAM_ALGORITHM lstm | none)
     downstream_algorithm: str = "lstm"
     # --- MI355X engine knobs -------------------------------------------------------
@@ -165,6 +168,10 @@ class BrainConfig:
         c.max_cache_size = int(f("MAX_CACHE_SIZE", c.max_cache_size, int))
         c.lstm_threshold = f("ML_LSTM_THRESHOLD", c.lstm_threshold)
         c.lstm_level_threshold = f("FOREMAST_LSTM_LEVEL_THRESHOLD", c.lstm_level_threshold)
+        attribution = (e.get("FOREMAST_LSTM_ATTRIBUTION") or "0").strip()
+        if attribution not in ("0", "1"):
+            raise ValueError(f"FOREMAST_LSTM_ATTRIBUTION must be 0 or 1, not {attribution!r}")
+        c.lstm_attribution = attribution == "1"
         c.downstream_algorithm = (e.get("ML_DOWNSTREAM_ALGORITHM") or c.downstream_algorithm).strip().lower()
         c.dtype = (e.get("FOREMAST_DTYPE") or c.dtype).strip().lower()
         if c.dtype not in RING_DTYPES:
