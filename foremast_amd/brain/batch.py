@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ..models import bivariate as biv_ref
+from ..models import multivariate_normal as mvn_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
 from ..models import pairwise as pw_ref
@@ -120,7 +121,7 @@ class BatchScorer:
                 algo = "double_exponential_smoothing"
             if algo == "seasonal_decompose" and len(t.hist) < 2 * m + 1:
                 algo = "moving_average_all"  # needs more than two seasons of history
-            if algo in ("bivariate_normal", "lstm", "auto"):
+            if algo in ("bivariate_normal", "multivariate_normal", "lstm", "auto"):
                 algo = "moving_average_all"  # per-metric part; the joint model runs in the worker
             groups.setdefault((algo, m if algo in ("holt_winters", "seasonal_decompose") else 0), []).append(i)
         for (algo, m), idx in groups.items():
@@ -303,4 +304,64 @@ class BatchScorer:
             pts = [(float(cts[j]), float(cur2[j, 0])) for j in range(len(cts)) if d2[i, j] > t2[i]]
             res.append((int(verdict[i]) if not pts else 1, pts))
         self.series_scored += 2 * B
+        return res
+
+    def score_mvn(self, groups: List[List[MetricTask]]) -> List[Tuple[int, Dict[int, List[Tuple[float, float]]]]]:
+        """Score the metric groups (2..8 metrics of one job each) with the k-variate normal
+        (``models/multivariate_normal.py``): histories and current points aligned by
+        :func:`~.multivariate.align_job`, threshold ``q_k(thr)`` of the group's first metric.
+        Returns per group (verdict, {index of a named metric: its anomalous points as
+        (timestamp, its own value)}).  On a GPU every group's rows are stacked into one fp32
+        ``[sum k, T]`` tensor and scored by ``kernels.mvn_groups`` (head 0, one pod, the aligned
+        points as the window); on the CPU the reference scores them."""
+        from .multivariate import align_job
+        if not groups:
+            return []
+        aligned = [align_job(g) for g in groups]
+        ks = [len(g) for g in groups]
+        T = max(max(h.shape[0] for h, _, _ in aligned), 1)
+        C = max(max(len(cts) for _, cts, _ in aligned), 1)
+        thr2 = torch.tensor([mvn_ref.chi2_threshold(float(np.float32(g[0].threshold)), k) for g, k in zip(groups, ks)],
+                            dtype=torch.float32)
+        res: List[Tuple[int, Dict[int, List[Tuple[float, float]]]]] = []
+        if self.gpu:
+            from ..ops import kernels as K
+            n = sum(ks)
+            ld = (T + 3) // 4 * 4     # rows 16-byte aligned: the kernel's vector path
+            hist = np.full((n, ld), np.nan, dtype=np.float32)
+            cur = np.full((n, C), np.nan, dtype=np.float32)
+            table = np.full((len(groups), K.MVN_MAXK), -1, dtype=np.int32)
+            row = 0
+            for q, (h, cts, c) in enumerate(aligned):
+                k = ks[q]
+                hist[row:row + k, T - h.shape[0]:T] = h.T
+                cur[row:row + k, :len(cts)] = c.T
+                table[q, :k] = np.arange(row, row + k)
+                row += k
+            ab = K.AnomalyBuffer(n * C, self.device)
+            ab.reset()
+            out = K.mvn_groups(torch.from_numpy(hist).to(self.device)[:, :T], 0, T, table,
+                               torch.from_numpy(cur).to(self.device), 1, C,
+                               torch.zeros(n, dtype=torch.float32, device=self.device), thr2=thr2.to(self.device),
+                               min_valid=self.cfg.min_historical_points, anomalies=ab)
+            verdict = out["verdict"].cpu().numpy()
+            rows, cols, vals, _ = ab.fetch()
+            owner = np.repeat(np.arange(len(groups)), ks)
+            first = np.concatenate([[0], np.cumsum(ks)[:-1]])
+            named: List[Dict[int, List[Tuple[float, float]]]] = [{} for _ in groups]
+            for rr, cc, vv in zip(rows.tolist(), cols.tolist(), vals.tolist()):
+                q = int(owner[rr])
+                named[q].setdefault(rr - int(first[q]), []).append((float(aligned[q][1][cc]), float(vv)))
+            for q in range(len(groups)):
+                res.append((int(verdict[q]), {i: sorted(p) for i, p in named[q].items()}))
+        else:
+            for q, (h, cts, c) in enumerate(aligned):
+                fit = mvn_ref.fit_mvn(torch.from_numpy(h)[None])
+                x = torch.from_numpy(c)[None] if len(cts) else torch.full((1, 1, ks[q]), float("nan"))
+                s = mvn_ref.score_mvn(fit, x, thr2[q:q + 1], self.cfg.min_historical_points)
+                pts: Dict[int, List[Tuple[float, float]]] = {}
+                for j, i in zip(*np.nonzero(s.names[0].numpy())):
+                    pts.setdefault(int(i), []).append((float(cts[j]), float(c[j, i])))
+                res.append((int(s.verdict[0]), pts))
+        self.series_scored += sum(ks)
         return res

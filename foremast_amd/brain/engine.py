@@ -27,6 +27,7 @@ import torch
 
 from ..ingest.ringbuffer import HistoryRing, WindowRing
 from ..models import bivariate as biv_ref
+from ..models import multivariate_normal as mvn_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
 from ..models import pairwise as pw_ref
@@ -144,6 +145,12 @@ class StreamingShard:
         self.pairs: Optional[np.ndarray] = None         # host [Np, 2] (row of metric 0, row of metric 1)
         self._pairs_dev: Optional[torch.Tensor] = None
         self._joint_out: Dict[str, torch.Tensor] = {}
+        # joint k-variate normal over row groups (set_groups): the same place in the tick
+        self.groups: Optional[np.ndarray] = None        # host [Ng, 8] rows padded with -1
+        self.group_k: Optional[np.ndarray] = None       # host [Ng] metrics per group
+        self._groups_dev: Optional[torch.Tensor] = None
+        self._groups_kmask = 0
+        self._groups_thr2: Optional[torch.Tensor] = None  # [Ng] q_k(thr), rebuilt after a threshold change
 
     def refresh_thresholds(self) -> None:
         """Per-point thresholds of the full and the lowered (pairwise) band for the
@@ -154,6 +161,7 @@ class StreamingShard:
             self.threshold, self.bound, C, self.cfg.pairwise_scale, self.cfg.window_correction)
         self.thr_full = self.thr_full.to(self.device).contiguous()
         self.thr_low = self.thr_low.to(self.device).contiguous()
+        self._groups_thr2 = None
 
     def enable_anomaly_list(self, cap: int) -> None:
         if self.gpu:
@@ -167,6 +175,8 @@ class StreamingShard:
         ``joint_verdict`` / ``joint_d2`` / ``joint_count`` / ``joint_mean`` / ``joint_cov``;
         a flagged pair raises its first row's verdict (counted once per row in the per-app
         table, not at all if the row was flagged already)."""
+        if pairs is not None and self.groups is not None:
+            raise ValueError("a shard scores row pairs or row groups, not both")
         self._joint_out = {}
         if pairs is None:
             self.pairs = self._pairs_dev = None
@@ -176,6 +186,39 @@ class StreamingShard:
             raise ValueError(f"pair rows outside [0, {self.spec.n_series})")
         self.pairs = p
         self._pairs_dev = torch.from_numpy(p).to(self.device)
+
+    def set_groups(self, groups) -> None:
+        """Row groups (the 2..8 metrics of a job) scored jointly by the k-variate normal after
+        the per-row scorer (``models/multivariate_normal.py``; GPU: ``ops/csrc/mvn_groups.hip``):
+        a host int array ``[Ng, <= 8]`` padded with -1 or a list of row lists, or None for no
+        joint model.  ``score()`` then adds ``joint_verdict`` / ``joint_d2`` / ``joint_count`` /
+        ``joint_blame`` / ``joint_mean`` / ``joint_cov`` (and ``joint_contrib`` / ``joint_thr2``);
+        a flagged group raises the row verdict of every named metric (each counted once per row
+        in the per-app table, not at all if the row was flagged already)."""
+        if groups is not None and self.pairs is not None:
+            raise ValueError("a shard scores row pairs or row groups, not both")
+        self._joint_out = {}
+        self._groups_thr2 = None
+        if groups is None:
+            self.groups = self.group_k = self._groups_dev = None
+            return
+        from ..ops.kernels import KernelShapeError, mvn_group_table
+        try:
+            table, k, kmask = mvn_group_table(groups, self.spec.n_series)
+        except KernelShapeError as e:
+            raise ValueError(str(e)) from None
+        if table.shape[0] and int(k.min()) < 2:
+            raise ValueError("a group takes at least 2 rows")
+        self.groups, self.group_k, self._groups_kmask = table, k, kmask
+        self._groups_dev = torch.from_numpy(table).to(self.device)
+
+    def _group_thr2(self) -> torch.Tensor:
+        if self._groups_thr2 is None:
+            thr = self.threshold.float().cpu().numpy()[self.groups[:, 0]]
+            self._groups_thr2 = torch.tensor([mvn_ref.chi2_threshold(float(t), int(k))
+                                              for t, k in zip(thr, self.group_k)],
+                                             dtype=torch.float32).to(self.device)
+        return self._groups_thr2
 
     # ------------------------------------------------------------------ data in
     def load_history(self, values: torch.Tensor) -> None:
@@ -429,6 +472,8 @@ class StreamingShard:
             # The joint pass is not part of tick_graph: the monitors that set pairs score the
             # rows with moving_average_all, for which graph_ready() is never true.
             self._score_joint(out)
+        if self.groups is not None:
+            self._score_groups(out)   # not part of tick_graph either, for the same reason
         return out
 
     def _score_joint(self, out: Dict[str, torch.Tensor]) -> None:
@@ -480,6 +525,61 @@ class StreamingShard:
                                   torch.ones_like(new, dtype=torch.int32), accumulate=True)
         return {"mean": fit.mean, "cov": fit.cov, "nvalid": fit.count, "d2": d2, "count": count,
                 "verdict": verdict, "score": score}
+
+    def _score_groups(self, out: Dict[str, torch.Tensor]) -> None:
+        """The k-variate normal of every row group, refitted from the ring like the per-row
+        scorers; threshold: q_k of the raw per-row one of the group's first row."""
+        cfg, h = self.cfg, self.hist
+        rv = self._joint_out.get("row_verdict")
+        if rv is None:
+            rv = torch.empty_like(out["verdict"])
+        out["row_verdict"] = rv.copy_(out["verdict"])
+        thr2 = self._group_thr2()
+        if self.gpu:
+            from ..ops import kernels as K
+            j = K.mvn_groups(h.data, h.head, h.length, self._groups_dev, self.cur.data, self.cur.P,
+                             self.cur.W, self.threshold, thr2=thr2, kmask=self._groups_kmask,
+                             min_valid=cfg.min_historical_points, verdict=out["verdict"], app_id=self.app_id, app_stats=self.app_stats,
+                             anomalies=self.anomalies, contrib=True, out=self._joint_out)
+        else:
+            j = self._groups_cpu(out, thr2)
+        j["row_verdict"] = rv
+        self._joint_out = j
+        for k in ("verdict", "d2", "count", "blame", "mean", "cov", "contrib"):
+            out["joint_" + k] = j[k]
+        out["joint_thr2"] = thr2
+
+    def _groups_cpu(self, out: Dict[str, torch.Tensor], thr2: torch.Tensor) -> Dict[str, torch.Tensor]:
+        cfg = self.cfg
+        P, W = self.cur.P, self.cur.W
+        Ng = self.groups.shape[0]
+        y = self.hist.logical().float()
+        cm = torch.nanmean(self.cur.data.view(-1, P, W), 1)          # pod means [N, W]
+        nan = float("nan")
+        j = {"mean": torch.zeros((Ng, mvn_ref.MAX_K)), "cov": torch.zeros((Ng, 36)), "nvalid": torch.zeros(Ng),
+             "d2": torch.full((Ng, W), nan), "count": torch.zeros(Ng, dtype=torch.int32),
+             "verdict": torch.full((Ng,), -1, dtype=torch.int8), "score": torch.zeros(Ng),
+             "blame": torch.zeros(Ng, dtype=torch.int32), "contrib": torch.zeros((Ng, W, mvn_ref.MAX_K))}
+        named_rows = []
+        for k in sorted(set(self.group_k.tolist())):   # one batched reference call per group size
+            sel = torch.from_numpy(np.nonzero(self.group_k == k)[0])
+            g = torch.from_numpy(self.groups[sel.numpy(), :k]).long()   # [n, k]
+            fit = mvn_ref.fit_mvn(y[g].permute(0, 2, 1))
+            x = cm[g].permute(0, 2, 1)                                   # [n, W, k]
+            s = mvn_ref.score_mvn(fit, x, thr2[sel], cfg.min_historical_points)
+            j["mean"][sel, :k], j["cov"][sel, :k * (k + 1) // 2], j["nvalid"][sel] = fit.mean, fit.cov, fit.count
+            j["d2"][sel], j["count"][sel], j["verdict"][sel], j["blame"][sel] = s.d2, s.count, s.verdict, s.blame
+            j["contrib"][sel, :, :k] = s.contrib
+            valid = ~torch.isnan(s.d2)
+            j["score"][sel] = torch.where(valid, s.d2.clamp(min=0).sqrt(), torch.zeros_like(s.d2)).amax(1)
+            named_rows.append(g[s.names.any(1)])
+        rows = torch.unique(torch.cat(named_rows)) if named_rows else torch.zeros(0, dtype=torch.long)
+        rv = out["verdict"]
+        new = rows[rv[rows] != 1]   # rows the per-row pass had not flagged: counted once each
+        rv[new] = 1
+        self.app_stats.index_put_((self.app_id[new].long(), torch.zeros_like(new)),
+                                  torch.ones_like(new, dtype=torch.int32), accumulate=True)
+        return j
 
     # ------------------------------------------------------------------ model cache
     def cache_supported(self) -> bool:

@@ -46,20 +46,25 @@ UNIVARIATE = ("holt_winters", "exponential_smoothing", "double_exponential_smoot
               "moving_average_all", "seasonal_decompose", "prophet")
 # multi-metric algorithms (docs/guides/design.md:53-89): every metric keeps a univariate
 # row (moving_average_all, as brain/batch.py scores it), and the job gets a joint model
-JOINT_ALGORITHMS = ("bivariate_normal", "lstm", "auto")
+JOINT_ALGORITHMS = ("bivariate_normal", "multivariate_normal", "lstm", "auto")
 ALGORITHMS = UNIVARIATE + JOINT_ALGORITHMS
-JOINT_SERVED = ("biv", "lstm")   # joint models the resident engine serves
+# joint models the resident engine serves ("mvn" needs an admission-time k x k state per job:
+# such rollout jobs stay with BrainWorker)
+JOINT_SERVED = ("biv", "lstm")
 
 
 def joint_kind(algorithm: str, n_metrics: int) -> Optional[str]:
     """The joint model of a job with ``n_metrics`` aliases: ``"biv"`` (bivariate
-    normal over its first two aliases), ``"lstm"`` (LSTM autoencoder over all) or
+    normal over its first two aliases), ``"mvn"`` (k-variate normal over all, at most
+    the first 8), ``"lstm"`` (LSTM autoencoder over all) or
     None — the dispatch of ``brain/worker.py`` ``_multivariate``: ``auto`` sends 2
     metrics to the bivariate normal and 3+ to the LSTM (``design.md:76-84``)."""
     if algorithm == "auto":
         return "biv" if n_metrics == 2 else ("lstm" if n_metrics >= 3 else None)
     if algorithm == "bivariate_normal":
         return "biv" if n_metrics >= 2 else None
+    if algorithm == "multivariate_normal":
+        return "mvn" if n_metrics >= 2 else None
     if algorithm == "lstm":
         return "lstm" if n_metrics >= 2 else None
     return None

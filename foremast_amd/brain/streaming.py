@@ -30,7 +30,10 @@ series resident in one :class:`~foremast_amd.brain.engine.StreamingShard`:
   rows also form a pair of the shard (``StreamingShard.set_pairs``): the bivariate
   normal is refitted from the ring and scored on the window every tick in one more
   launch, and a broken relation between the two metrics fails the job even when
-  each metric stays inside its own band.
+  each metric stays inside its own band.  Under multivariate_normal the rows of all
+  aliases of a job with two or more metrics (at most 8) form a group instead
+  (``StreamingShard.set_groups``, ``models/multivariate_normal.py``): the k-variate
+  normal, one launch, and the metrics behind a verdict are named.
 """
 
 from __future__ import annotations
@@ -158,6 +161,10 @@ class StreamingMonitor:
         # jobs and their rows, rebuilt when either changes, never stored in a snapshot
         self.pairs: List[Tuple[int, int]] = []       # distinct (row of alias 0, row of alias 1)
         self.job_pair: Dict[str, int] = {}           # job id -> index into pairs
+        # joint k-variate normal of the jobs with plans.joint_kind == "mvn": the same derived state
+        self.groups: List[Tuple[int, ...]] = []      # distinct row tuples (aliases in sorted order, at most 8)
+        self.job_group: Dict[str, int] = {}          # job id -> index into groups
+        self._wide_warned: Set[str] = set()
         self._pairs_dirty = True
 
     # ------------------------------------------------------------------ membership
@@ -208,8 +215,8 @@ class StreamingMonitor:
     # ------------------------------------------------------------------ rows
     def _new_shard(self, capacity: int) -> StreamingShard:
         season = max(2, int(round(86400.0 / self.step)))
-        # the multi-metric algorithms (bivariate_normal, auto, lstm) score each row with
-        # moving_average_all; the bivariate normal's pairs come on top (_rebuild_pairs)
+        # the multi-metric algorithms (bivariate_normal, multivariate_normal, auto, lstm) score each
+        # row with moving_average_all; the pairs or groups come on top (_rebuild_pairs)
         algo = self.cfg.algorithm if self.cfg.algorithm in ("holt_winters", "exponential_smoothing",
                                                             "double_exponential_smoothing", "moving_average",
                                                             "moving_average_all", "seasonal_decompose",
@@ -298,6 +305,7 @@ class StreamingMonitor:
         self._pairs_dirty = False
         index: Dict[Tuple[int, int], int] = {}
         self.job_pair = {}
+        self._rebuild_groups()
         for jid, job in self.jobs.items():
             if joint_kind(self.cfg.algorithm, len(job.series)) != "biv":
                 continue
@@ -308,7 +316,38 @@ class StreamingMonitor:
             self.job_pair[jid] = index.setdefault((r0, r1), len(index))
         self.pairs = list(index)
         if self.shard is not None:
-            self.shard.set_pairs(np.array(self.pairs, dtype=np.int32) if self.pairs else None)
+            if self.groups:   # one algorithm, one joint model: a shard never holds both tables
+                self.shard.set_pairs(None)
+                self.shard.set_groups([list(g) for g in self.groups])
+            else:
+                self.shard.set_groups(None)
+                self.shard.set_pairs(np.array(self.pairs, dtype=np.int32) if self.pairs else None)
+
+    def _rebuild_groups(self) -> None:
+        """The group table from the live jobs, derived exactly as the pair table is: a job whose
+        joint model is the k-variate normal groups the rows of all its aliases in sorted order
+        (the first 8 of a job with more, with one warning per job).  Jobs on the same series in
+        the same order share one group."""
+        from ..models.multivariate_normal import MAX_K
+        from .plans import joint_kind
+        index: Dict[Tuple[int, ...], int] = {}
+        self.job_group = {}
+        for jid, job in self.jobs.items():
+            if joint_kind(self.cfg.algorithm, len(job.series)) != "mvn":
+                continue
+            aliases = sorted(job.series)
+            if len(aliases) > MAX_K:
+                if jid not in self._wide_warned:
+                    self._wide_warned.add(jid)
+                    log.warning("job %s has %d metrics: multivariate_normal models the first %d (%s)", jid,
+                                len(aliases), MAX_K, ",".join(aliases[:MAX_K]))
+                aliases = aliases[:MAX_K]
+            rows = tuple(self.rows.get(job.series[a]) for a in aliases)
+            if any(row is None for row in rows):
+                continue
+            self.job_group[jid] = index.setdefault(rows, len(index))
+        self.groups = list(index)
+        self._wide_warned &= set(self.jobs)
 
     def _refresh_apps(self) -> None:
         """App roster of the live series (index = row of the per-app counters)."""
@@ -489,6 +528,38 @@ class StreamingMonitor:
             res[q] = [v for p in pts for v in p]
         return res
 
+    def _group_points(self, out, col: int) -> Dict[int, Dict[int, List[float]]]:
+        """Flagged group -> {index of a named metric: its points ``[ts, v, ...]``}: the slots whose
+        squared Mahalanobis distance exceeds q_k(thr) and on which the metric is named
+        (``models/multivariate_normal.py``), dated like the pair points, valued by the metric's
+        own pod mean."""
+        from ..models import multivariate_normal as mvn_ref
+        jv = out["joint_verdict"].cpu().numpy()
+        hit = np.nonzero(jv == 1)[0]
+        if hit.size == 0:
+            return {}
+        sh = self.shard
+        idx = torch.from_numpy(hit).to(self.device)
+        d2 = out["joint_d2"][idx].float().cpu()
+        contrib = out["joint_contrib"][idx].float().cpu()
+        thr2 = out["joint_thr2"][idx].float().cpu()
+        res: Dict[int, Dict[int, List[float]]] = {}
+        for i, q in enumerate(hit.tolist()):
+            rows = list(self.groups[q])
+            k = len(rows)
+            flag = d2[i] > thr2[i]                                   # NaN slots compare False
+            names = (mvn_ref.named(contrib[i, :, :k], d2[i]) & flag[:, None]).numpy()
+            r_t = torch.tensor(rows, dtype=torch.long, device=self.device)
+            x = torch.nanmean(sh.cur.data[r_t].view(k, sh.cur.P, self.W), 1).cpu().numpy()
+            per: Dict[int, List[float]] = {}
+            for m in range(k):
+                pts = sorted((self.t_last - ((col - c) % self.W) * self.step, float(x[m, c]))
+                             for c in np.nonzero(names[:, m])[0].tolist())
+                if pts:
+                    per[m] = [v for p in pts for v in p]
+            res[q] = per
+        return res
+
     async def tick(self) -> Dict[str, str]:
         """One scoring tick over every continuous series; returns job → status written."""
         await self._apply_changes()
@@ -509,14 +580,18 @@ class StreamingMonitor:
         upper = out["upper"][:, col].float().cpu().numpy() if "upper" in out else None
         lower = out["lower"][:, col].float().cpu().numpy() if "lower" in out else None
         points: Dict[int, List[Tuple[float, float]]] = {}
-        joint = self._joint_points(out, col) if "joint_verdict" in out else {}
+        grouped = "joint_blame" in out
+        joint = self._joint_points(out, col) if "joint_verdict" in out and not grouped else {}
+        gjoint = self._group_points(out, col) if grouped else {}
         ab = self.shard.anomalies
         overflow = False
         if ab is not None:  # K9 device-side compaction: only the anomalies come back
             rows, cols, vals, overflow = ab.fetch()
             # the list also holds the joint model's triples under each flagged pair's first row:
             # a row flagged by both takes its per-row points from the bands below
-            both = sorted({self.pairs[q][0] for q in joint if verdict[self.pairs[q][0]] == 1})
+            # (a flagged group's, under the row of each named metric)
+            jrows = {self.pairs[q][0] for q in joint} | {self.groups[q][m] for q, per in gjoint.items() for m in per}
+            both = sorted(row for row in jrows if verdict[row] == 1)
             if both and not overflow:
                 keep = ~np.isin(rows, both)
                 r2, c2, v2 = self._band_points(out, verdict, np.array(both, dtype=np.int64))
@@ -549,6 +624,12 @@ class StreamingMonitor:
             if q in joint:
                 # the joint points replace the first alias's own list (worker.py _multivariate)
                 anomaly[sorted(job.series)[0]] = {"tags": "", "values": joint[q]}
+            g = self.job_group.get(jid)
+            if g in gjoint:
+                # every named alias carries the joint points, which replace its own list
+                aliases = sorted(job.series)
+                for m, vals in gjoint[g].items():
+                    anomaly[aliases[m]] = {"tags": "", "values": vals}
             if anomaly:
                 status, reason = r.ST_COMPLETED_UNHEALTH, "anomaly detected in " + ",".join(sorted(anomaly))
             elif now >= job.end_ts:

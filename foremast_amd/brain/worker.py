@@ -241,12 +241,13 @@ class BrainWorker:
 
     def _multivariate(self, plans: List[JobPlan], per_job) -> None:
         """Joint models on top of the per-metric verdicts: ``bivariate_normal``
-        (>= 2 metrics, first two aliases), ``lstm`` (>= 2 metrics), or
+        (>= 2 metrics, first two aliases), ``multivariate_normal`` (>= 2 metrics, all
+        aliases up to the first 8 in sorted order), ``lstm`` (>= 2 metrics), or
         ``auto`` = the design doc's dispatch (2 metrics → bivariate normal,
         3+ → LSTM autoencoder; ``docs/guides/design.md:76-84``)."""
         self._downstream(per_job)
         algo = self.cfg.algorithm
-        if algo not in ("bivariate_normal", "lstm", "auto"):
+        if algo not in ("bivariate_normal", "multivariate_normal", "lstm", "auto"):
             return
         # per-caller (downstream) tasks are scored jointly per caller by _downstream
         per_job = {i: [(t, r_) for t, r_ in items if not t.split_label] for i, items in per_job.items()}
@@ -255,6 +256,9 @@ class BrainWorker:
         if lstm_jobs:
             self._score_lstm(per_job, lstm_jobs)
         if algo == "lstm":
+            return
+        if algo == "multivariate_normal":
+            self._score_mvn(per_job)
             return
         pairs, owners = [], []
         for i, items in per_job.items():
@@ -269,6 +273,30 @@ class BrainWorker:
                 ra.verdict = max(ra.verdict, 1)
                 ra.anomalies = [(ts, v, "") for ts, v in pts]
                 ra.model = rb.model = "bivariate_normal"
+
+    def _score_mvn(self, per_job) -> None:
+        """The k-variate normal over all aliases of a job in sorted order (the first 8 of a
+        job with more): every named alias gets verdict 1 and the joint points."""
+        from ..models.multivariate_normal import MAX_K
+        groups, owners = [], []
+        for i, items in per_job.items():
+            if len(items) < 2:
+                continue
+            items = sorted(items, key=lambda tr: tr[0].alias)
+            if len(items) > MAX_K:
+                log.warning("job %s has %d metrics: multivariate_normal models the first %d (%s)",
+                            items[0][0].job_id, len(items), MAX_K, ",".join(t.alias for t, _ in items[:MAX_K]))
+                items = items[:MAX_K]
+            groups.append([t for t, _ in items])
+            owners.append(items)
+        for items, (verdict, named) in zip(owners, self.scorer.score_mvn(groups)):
+            for _t, res in items:
+                res.model = "multivariate_normal"
+            if verdict == 1:
+                for f, pts in named.items():
+                    res = items[f][1]
+                    res.verdict = max(res.verdict, 1)
+                    res.anomalies = [(ts, v, "") for ts, v in pts]
 
     def _downstream(self, per_job) -> None:
         """Downstream impact / API level: for every caller (or request path) of the

@@ -10,6 +10,7 @@ K2/K3       ``smooth_fit`` (ES/DES/HW)    models/smoothing.py
 K5/K11      ``rank_tests``                models/pairwise.py
 K6/K7       ``lstm_*``                    models/lstm_ae.py
 K8          ``bivariate``                 models/bivariate.py
+K8 (k <= 8) ``mvn_groups``                models/multivariate_normal.py
 K9          fused detection epilogue      models/detect.py
 K10         ``ring_append``               ingest/ringbuffer.py
 ==========  ============================  ==========================================

@@ -93,6 +93,19 @@ class BivPairArgs(C.Structure):
     ]
 
 
+class MvnGroupArgs(C.Structure):
+    _fields_ = [
+        ("hist", P), ("ld", LL), ("ring_len", I), ("head", I), ("len", I), ("N", I),
+        ("groups", P), ("Ng", I), ("P", I), ("cur", P), ("ld_cur", LL), ("W", I), ("min_valid", I),
+        ("thr2", P), ("eps", F), ("anom_cap", I),
+        ("mean", P), ("cov", P), ("nvalid", P), ("d2", P), ("count", P), ("verdict", P), ("score", P),
+        ("blame", P), ("contrib", P),
+        ("row_verdict", P), ("app_id", P), ("app_stats", P), ("raised", P),
+        ("anom_count", P), ("anom_series", P), ("anom_col", P), ("anom_val", P),
+        ("kmask", I), ("_pad", I),
+    ]
+
+
 class LstmArgs(C.Structure):
     pass  # populated in lstm bindings (see kernels.py)
 
@@ -149,6 +162,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.fm_bivariate.restype = I
     lib.fm_bivariate_pairs.argtypes = [C.POINTER(BivPairArgs), I, P]
     lib.fm_bivariate_pairs.restype = I
+    lib.fm_mvn_groups.argtypes = [C.POINTER(MvnGroupArgs), I, P]
+    lib.fm_mvn_groups.restype = I
     lib.fm_ring_append.argtypes = [P, LL, I, I, I, P, LL, LL, I, P]
     lib.fm_ring_append.restype = I
     lib.fm_ring_append_dev.argtypes = [P, LL, I, I, P, I, P, LL, LL, I, P]

@@ -11,6 +11,7 @@ extern "C" long long fm_abi_sizeof(const char* name) {
   if (!__builtin_strcmp(name, "WindowArgs")) return sizeof(WindowArgs);
   if (!__builtin_strcmp(name, "BivArgs")) return sizeof(BivArgs);
   if (!__builtin_strcmp(name, "BivPairArgs")) return sizeof(BivPairArgs);
+  if (!__builtin_strcmp(name, "MvnGroupArgs")) return sizeof(MvnGroupArgs);
   return -1;
 }
 
@@ -24,5 +25,6 @@ extern "C" long long fm_abi_offsetof(const char* name, const char* field) {
   if (!__builtin_strcmp(name, "WindowArgs")) { FM_OFF(WindowArgs, det); }
   if (!__builtin_strcmp(name, "BivArgs")) { FM_OFF(BivArgs, eps); FM_OFF(BivArgs, app_stats); }
   if (!__builtin_strcmp(name, "BivPairArgs")) { FM_OFF(BivPairArgs, threshold); FM_OFF(BivPairArgs, anom_val); }
+  if (!__builtin_strcmp(name, "MvnGroupArgs")) { FM_OFF(MvnGroupArgs, thr2); FM_OFF(MvnGroupArgs, contrib); FM_OFF(MvnGroupArgs, anom_val); FM_OFF(MvnGroupArgs, kmask); }
   return -1;
 }

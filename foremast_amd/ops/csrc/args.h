@@ -194,3 +194,49 @@ struct BivPairArgs {
   int* anom_col;
   float* anom_val;
 };
+
+// The k-variate normal over row groups of ONE ring (2 <= k <= 8 metrics of a job): the
+// generalisation of BivPairArgs.  The threshold arrives as thr2 = q_k(thr), the chi^2_k
+// quantile computed on the host (models/multivariate_normal.py).
+#define FM_MVN_MAXK 8
+#define FM_MVN_TRI 36     // packed lower triangle of an 8 x 8 covariance
+struct MvnGroupArgs {
+  const void* hist;       // [N, ld] ring (float or bf16)
+  long long ld;
+  int ring_len;
+  int head;
+  int len;
+  int N;
+  const int* groups;      // [Ng, 8] rows padded with -1; k = leading non-negative entries
+  int Ng;
+  int P;                  // pods per window slot
+  const float* cur;       // [N, ld_cur], column p * W + slot
+  long long ld_cur;
+  int W;
+  int min_valid;
+  const float* thr2;      // [Ng] q_k(thr) of the group's first row
+  float eps;
+  int anom_cap;
+  float* mean;            // [Ng, 8] (unused entries 0)
+  float* cov;             // [Ng, 36] packed lower triangle, row-major (unused entries 0)
+  float* nvalid;          // [Ng]
+  float* d2;              // [Ng, W]
+  int* count;             // [Ng]
+  signed char* verdict;   // [Ng]
+  float* score;           // [Ng] max d
+  int* blame;             // [Ng] bit i: metric i named on an anomalous slot
+  float* contrib;         // [Ng, W, 8] or null
+  // shard state (optional): a flagged group raises the row of every named metric, each
+  // counted once per row and tick in app_stats[2 * app_id[row]] unless flagged already
+  signed char* row_verdict; // [N] or null
+  const int* app_id;        // [N] or null
+  int* app_stats;           // [A, 2] or null
+  int* raised;              // [N] scratch, zeroed by the caller (needed with row_verdict)
+  // K9 compaction (optional): (row of a named metric, slot, pod mean of that metric)
+  int* anom_count;
+  int* anom_series;
+  int* anom_col;
+  float* anom_val;
+  int kmask;              // bit k: some group may have k rows (0: unknown, every k is launched)
+  int _pad;
+};

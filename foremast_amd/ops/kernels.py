@@ -924,6 +924,133 @@ def bivariate_pairs(hist: torch.Tensor, head: int, length: int, pairs, cur: torc
     return out
 
 
+MVN_MAXK = 8    # args.h FM_MVN_MAXK
+MVN_TRI = 36    # args.h FM_MVN_TRI
+
+
+def mvn_group_table(groups, n_rows: int):
+    """A host group table as contiguous int32 ``[Ng, 8]`` padded with -1, and the bit mask
+    of the group sizes in it.  ``groups``: a numpy / CPU integer array ``[Ng, <= 8]`` padded
+    with negative entries, or a sequence of row sequences; a group of more than 8 rows and a
+    row outside ``[0, n_rows)`` raise ``KernelShapeError``."""
+    import numpy as np
+    if isinstance(groups, torch.Tensor):
+        groups = groups.numpy()
+    if not isinstance(groups, np.ndarray):
+        rows = [list(g) for g in groups]
+        _need(all(len(g) <= MVN_MAXK for g in rows), f"a group takes at most {MVN_MAXK} rows")
+        groups = np.array([g + [-1] * (MVN_MAXK - len(g)) for g in rows], dtype=np.int64).reshape(-1, MVN_MAXK)
+    host = groups.reshape(-1, MVN_MAXK) if groups.size == 0 else groups
+    _need(host.ndim == 2 and host.dtype.kind in "iu", "groups must be integer [Ng, k]")
+    lead = np.cumprod(host >= 0, axis=1).astype(bool)     # the leading non-negative entries
+    k = lead.sum(1)
+    _need(host.size == 0 or int(k.max()) <= MVN_MAXK, f"a group takes at most {MVN_MAXK} rows")
+    _need(not (lead & (host >= n_rows)).any(), f"group rows outside [0, {n_rows})")
+    table = np.full((host.shape[0], MVN_MAXK), -1, dtype=np.int32)
+    w = min(host.shape[1], MVN_MAXK)
+    table[:, :w] = np.where(lead[:, :w], host[:, :w], -1)
+    kmask = 0
+    for v in np.unique(k).tolist():
+        kmask |= 1 << max(int(v), 2)
+    return table, k.astype(np.int64), kmask
+
+
+def mvn_groups(hist: torch.Tensor, head: int, length: int, groups, cur: torch.Tensor, pods: int, window: int,
+               threshold: torch.Tensor, *, min_valid: int = 0, eps: float = 1e-9,
+               verdict: Optional[torch.Tensor] = None, app_id: Optional[torch.Tensor] = None,
+               app_stats: Optional[torch.Tensor] = None, anomalies: Optional[AnomalyBuffer] = None,
+               contrib: bool = False, thr2: Optional[torch.Tensor] = None, kmask: int = 0,
+               out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """The k-variate normal over row groups of one ring (``mvn_groups.hip``, semantics:
+    ``models/multivariate_normal.py``).  ``groups``: ``[Ng, 8]`` rows of ``hist`` padded with
+    -1 (k = the leading non-negative entries, 2..8) -- an int32 GPU tensor, or a numpy / CPU
+    array / list of row lists, which is range-checked here and copied to the device; ``cur``:
+    the ``[N, pods * window]`` window ring; ``threshold``: raw sigma units per row, read at a
+    group's first row and turned into ``thr2 = q_k(thr)`` on the host (a GPU group table needs
+    ``thr2 [Ng]`` from the caller, and may pass ``kmask``, the bit mask of the group sizes in it
+    (``mvn_group_table``): one launch per size present instead of one per size 2..8).  ``verdict`` (int8 ``[N]``, the shard's row verdicts),
+    ``app_id`` / ``app_stats`` and ``anomalies`` receive the effects of the flagged groups: every
+    named metric's row.  Outputs in ``out``: ``mean [Ng, 8]``, ``cov [Ng, 36]``, ``nvalid``,
+    ``d2 [Ng, window]``, ``count``, ``verdict``, ``score``, ``blame`` and, with ``contrib``,
+    ``contrib [Ng, window, 8]``."""
+    from ..models.multivariate_normal import chi2_threshold
+    lib = nat.require()
+    _hist_check(hist, head, length)
+    dev = hist.device
+    N = hist.shape[0]
+    P, W = int(pods), int(window)
+    _need(P >= 1 and W >= 1, "pods and window must be >= 1")
+    _vec(threshold, N, torch.float32, "threshold", dev)
+    kmask = int(kmask)
+    if not isinstance(groups, torch.Tensor) or not groups.is_cuda:
+        import numpy as np
+        table, k, kmask = mvn_group_table(groups, N)
+        if thr2 is None:
+            thr_h = threshold.detach().cpu().numpy()
+            first = np.where(k > 0, table[:, 0], 0)
+            thr2 = torch.tensor([chi2_threshold(float(t), max(int(kk), 1)) for t, kk in zip(thr_h[first], k)],
+                                dtype=torch.float32).to(dev)
+        groups = torch.from_numpy(table).to(dev)
+    _need(groups.dim() == 2 and groups.shape[1] == MVN_MAXK and groups.dtype == torch.int32
+          and groups.is_contiguous() and groups.device == dev,
+          f"groups must be contiguous int32 [Ng, {MVN_MAXK}] on the ring's device")
+    Ng = groups.shape[0]
+    _need(thr2 is not None, "a device group table needs thr2 [Ng] (chi2_threshold of each group)")
+    _vec(thr2, Ng, torch.float32, "thr2", dev)
+    _need(cur.dim() == 2 and cur.shape[0] == N and cur.shape[1] == P * W,
+          f"cur must be [{N}, {P * W}], got {tuple(cur.shape)}")
+    _need(cur.dtype == torch.float32 and cur.stride(1) == 1 and cur.device == dev,
+          "cur must be float32 with unit inner stride on the ring's device")
+    _vec(verdict, N, torch.int8, "verdict", dev)
+    _vec(app_id, N, torch.int32, "app_id", dev)
+    if app_id is not None:
+        _need(verdict is not None, "app_id needs the row verdicts")
+        _need(app_stats is not None and app_stats.dtype == torch.int32 and app_stats.is_contiguous()
+              and app_stats.dim() == 2 and app_stats.shape[1] == 2 and app_stats.device == dev,
+              "app_stats must be contiguous int32 [A, 2]")
+    out = {} if out is None else out
+    shapes = {"mean": ((Ng, MVN_MAXK), torch.float32), "cov": ((Ng, MVN_TRI), torch.float32),
+              "nvalid": ((Ng,), torch.float32), "d2": ((Ng, W), torch.float32), "count": ((Ng,), torch.int32),
+              "verdict": ((Ng,), torch.int8), "score": ((Ng,), torch.float32), "blame": ((Ng,), torch.int32)}
+    if contrib:
+        shapes["contrib"] = ((Ng, W, MVN_MAXK), torch.float32)
+    for k_, (shape, dt) in shapes.items():
+        if k_ not in out or tuple(out[k_].shape) != shape:
+            out[k_] = torch.empty(shape, dtype=dt, device=dev)
+    if not contrib:
+        out.pop("contrib", None)
+    if verdict is not None:
+        if "raised" not in out or out["raised"].shape[0] != N:
+            out["raised"] = torch.empty(N, dtype=torch.int32, device=dev)
+        out["raised"].zero_()
+    if Ng == 0:
+        return out
+    a = nat.MvnGroupArgs()
+    a.hist = nat.ptr(hist)
+    a.ld = hist.stride(0)
+    a.ring_len = hist.shape[1]
+    a.head, a.len, a.N = int(head), int(length), N
+    a.groups, a.Ng, a.P = nat.ptr(groups), Ng, P
+    a.cur, a.ld_cur, a.W = nat.ptr(cur), cur.stride(0), W
+    a.min_valid = int(min_valid)
+    a.thr2 = nat.ptr(thr2)
+    a.eps = float(eps)
+    for k_ in shapes:
+        setattr(a, k_, nat.ptr(out[k_]))
+    a.row_verdict = nat.ptr(verdict)
+    a.app_id = nat.ptr(app_id)
+    a.app_stats = nat.ptr(app_stats) if app_id is not None else 0
+    a.raised = nat.ptr(out["raised"]) if verdict is not None else 0
+    if anomalies is not None:
+        _need(anomalies.count.device == dev, "anomaly buffer on wrong device")
+        a.anom_count, a.anom_series, a.anom_col, a.anom_val = (nat.ptr(anomalies.count), nat.ptr(anomalies.series),
+                                                               nat.ptr(anomalies.col), nat.ptr(anomalies.val))
+        a.anom_cap = anomalies.cap
+    a.kmask = kmask
+    nat.check(lib.fm_mvn_groups(a, int(hist.dtype == torch.bfloat16), nat.stream_handle(dev)), "fm_mvn_groups")
+    return out
+
+
 def ring_append(dst: torch.Tensor, col0: int, src: torch.Tensor, col_dev: Optional[torch.Tensor] = None) -> None:
     """``dst[n, (col0 + j) % R] = src[n, j]`` (dst may be float32 or bf16); ``col_dev``
     (int32 device scalar): added to ``col0`` on the device (graph-captured ticks)."""

@@ -32,7 +32,7 @@ BOUND_BOTH = 3
 ALGORITHMS = (
     "moving_average", "moving_average_all", "exponential_smoothing",
     "double_exponential_smoothing", "holt_winters", "prophet", "seasonal_decompose",
-    "bivariate_normal", "lstm",
+    "bivariate_normal", "multivariate_normal", "lstm",
 )
 
 RING_DTYPES = ("bf16", "fp32")  # FOREMAST_DTYPE
