@@ -34,7 +34,7 @@ def test_ingest_from_pinned_host_matches_device_input():
 def test_copy_to_host_kernel():
     from foremast_amd.ops import kernels as K
     dev = torch.device("cuda:0")
-    for n in (1, 255, 256, 40_001):
+    for n in (1, 255, 256, 40_001, 300_000):  # 300,000 > 1024 blocks x 256: the grid-stride path
         src = torch.randint(-2**31, 2**31 - 1, (n,), dtype=torch.int32, device=dev)
         dst = torch.full((n,), 7, dtype=torch.int32).pin_memory()
         K.copy_to_host(dst, src)
