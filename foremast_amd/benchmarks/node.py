@@ -138,7 +138,7 @@ def _brainworker_share(docs, cfg) -> int:
     from ..brain import plans as pl
     from ..brain.lstm_monitor import lstm_features
     from ..brain.streaming import is_continuous
-    ps = pl.plan_many(list(docs), cfg.algorithm)
+    ps = pl.plan_many(list(docs), cfg.algorithm, joint_served=pl.joint_served_for(cfg))
     pl._PLANS.clear()
     return sum(1 for d, p in zip(docs, ps)
                if p is None and not (is_continuous(d) and lstm_features(d, cfg) is not None))

@@ -48,9 +48,16 @@ UNIVARIATE = ("holt_winters", "exponential_smoothing", "double_exponential_smoot
 # row (moving_average_all, as brain/batch.py scores it), and the job gets a joint model
 JOINT_ALGORITHMS = ("bivariate_normal", "multivariate_normal", "lstm", "auto")
 ALGORITHMS = UNIVARIATE + JOINT_ALGORITHMS
-# joint models the resident engine serves ("mvn" needs an admission-time k x k state per job:
-# such rollout jobs stay with BrainWorker)
+# joint models the resident engine serves by default ("mvn" needs an admission-time k x k state
+# per job: such rollout jobs stay with BrainWorker unless FOREMAST_ROLLOUT_MVN=1, joint_served_for)
 JOINT_SERVED = ("biv", "lstm")
+
+
+def joint_served_for(cfg) -> Tuple[str, ...]:
+    """The joint models the resident engine serves under ``cfg``: with
+    ``FOREMAST_ROLLOUT_MVN=1`` the engine keeps that k x k state (``brain/rollout.py``
+    ``_fit_joint``), so "mvn" jobs are planned too."""
+    return JOINT_SERVED + ("mvn",) if getattr(cfg, "rollout_mvn", False) else JOINT_SERVED
 
 
 def joint_kind(algorithm: str, n_metrics: int) -> Optional[str]:
@@ -558,12 +565,14 @@ def _remember(ck, plan) -> None:
         _PLANS.popitem(last=False)
 
 
-def plan_many(docs: Sequence[Dict], algorithm: str, step: float = 60.0,
-              window_cols: int = 11) -> List[Optional[RolloutPlan]]:
+def plan_many(docs: Sequence[Dict], algorithm: str, step: float = 60.0, window_cols: int = 11, *,
+              joint_served: Sequence[str] = JOINT_SERVED) -> List[Optional[RolloutPlan]]:
     """Plans of ``docs`` (None: not keyable by the resident engine), memoised per
     job id (content-addressed: a job's request, hence its plan, never changes).
     Unseen documents are decoded natively in one batch; the ones the native
-    decoder declines take the Python parser."""
+    decoder declines take the Python parser.  ``joint_served``: the joint models the
+    caller's engine serves (the filter is applied after the memo, which is keyed by job id
+    and geometry only)."""
     if algorithm not in ALGORITHMS:
         return [None] * len(docs)
     out: List[Optional[RolloutPlan]] = [None] * len(docs)
@@ -585,10 +594,11 @@ def plan_many(docs: Sequence[Dict], algorithm: str, step: float = 60.0,
         for i, p in enumerate(out):
             if p is not None:
                 k = joint_kind(algorithm, p.n)
-                if k is not None and k not in JOINT_SERVED:
+                if k is not None and k not in joint_served:
                     out[i] = None
     return out
 
 
-def plan_rollout(doc: Dict, algorithm: str, step: float = 60.0, window_cols: int = 11) -> Optional[RolloutPlan]:
-    return plan_many([doc], algorithm, step, window_cols)[0]
+def plan_rollout(doc: Dict, algorithm: str, step: float = 60.0, window_cols: int = 11, *,
+                 joint_served: Sequence[str] = JOINT_SERVED) -> Optional[RolloutPlan]:
+    return plan_many([doc], algorithm, step, window_cols, joint_served=joint_served)[0]

@@ -52,7 +52,11 @@ Multi-metric algorithms (``ML_ALGORITHM`` bivariate_normal / lstm / auto,
 add the job's joint model: the bivariate normal of its first two aliases (K8
 fit at admission, Mahalanobis on the pod-mean windows every tick) or the LSTM
 autoencoder over all of them (the node's resident LSTM engine,
-:mod:`.lstm_monitor`, fed each tick with the canary pods' mean).
+:mod:`.lstm_monitor`, fed each tick with the canary pods' mean).  Under
+``multivariate_normal`` the engine serves multi-metric jobs only with
+``FOREMAST_ROLLOUT_MVN=1``: the k-variate normal over all aliases (at most 8), a
+k x k state fitted at admission (``mvn_fit_state``) and scored every tick
+(``mvn_state_detect``), which names the metrics behind a verdict.
 
 Jobs the resident engine cannot key (non-Prometheus sources, per-caller /
 per-uri families, selectors that are not plain pod lists) stay with
@@ -78,6 +82,7 @@ from ..models import bivariate as biv_ref
 from ..models import decompose as dec_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
+from ..models import multivariate_normal as mvn_ref
 from ..models import pairwise as pw_ref
 from ..models import prophet_lite as pr_ref
 from ..models import smoothing as sm_ref
@@ -100,7 +105,7 @@ _NO_KEYS = np.zeros(0, dtype=np.uint64)
 def plan_rollout(doc: Dict, cfg: BrainConfig, step: float = 60.0, window_cols: int = 11) -> Optional[RolloutPlan]:
     """The rollout-table plan of a job, or None when the resident engine cannot
     key it (memoised per job id, see :func:`plans.plan_many`)."""
-    return pl.plan_rollout(doc, cfg.algorithm, step, window_cols)
+    return pl.plan_rollout(doc, cfg.algorithm, step, window_cols, joint_served=pl.joint_served_for(cfg))
 
 
 def is_rollout_keyable(doc: Dict, cfg: BrainConfig) -> bool:
@@ -231,6 +236,12 @@ class RolloutMonitor:
         # ML_ALGORITHM=prophet: rows keep the harmonic state of the window-scaled model
         # (models/prophet_lite.py window_state) and are scored by its own kernel
         self.prophet = self.cfg.algorithm == "prophet"
+        # FOREMAST_ROLLOUT_MVN=1 under ML_ALGORITHM=multivariate_normal: a multi-metric job keeps
+        # the k x k state of its joint normal on its first sorted alias's row (_fit_joint)
+        self._served = pl.joint_served_for(self.cfg)
+        self.mvn = self.cfg.rollout_mvn and self.cfg.algorithm == "multivariate_normal"
+        self._mvn_active = None   # (device int32 state rows of the live groups, their kmask); None: stale
+        self._mvn_out: Dict[str, torch.Tensor] = {}
         self.decode_threads = max(1, int(decode_threads or native.default_threads()))
         self.apps_per_query = max(1, int(apps_per_query))
         self.claim_limit = claim_limit
@@ -364,6 +375,12 @@ class RolloutMonitor:
             "biv_cov": torch.zeros((cap, 3), **f32),
             "biv_ok": torch.zeros(cap, dtype=torch.bool, device=dev),
         }
+        if self.mvn:  # joint k-variate normal of a multi-metric job, kept on its first sorted alias's row
+            new.update(mvn_mean=torch.zeros((cap, mvn_ref.MAX_K), **f32),
+                       mvn_cov=torch.zeros((cap, mvn_ref.STATE_TRI), **f32),
+                       mvn_chol=torch.zeros((cap, mvn_ref.STATE_TRI), **f32),
+                       mvn_nvalid=torch.zeros(cap, **f32), mvn_thr2=torch.zeros(cap, **f32),
+                       mvn_rows=torch.full((cap, mvn_ref.MAX_K), -1, dtype=torch.int32, device=dev))
         st = {k: torch.zeros(cap, **f32) for k in ("level", "trend", "sigma", "nvalid")}
         st["best"] = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         st["season_hb"] = torch.zeros((cap, HB), **f32)
@@ -396,6 +413,10 @@ class RolloutMonitor:
         ext("row_k", -1, np.int64)          # series index of the row within its job
         ext("last_anom", np.nan, np.float64)  # timestamp of the row's last anomalous point (band export)
         ext("biv_b", -1, np.int64)          # first-alias row of a bivariate job -> its second alias's row
+        if self.mvn:                        # host mirror of mvn_rows (group size, window rows)
+            ext("mvn_k", 0, np.int64)
+            ext("mvn_rows_h", -1, np.int64, (mvn_ref.MAX_K,))
+            self._mvn_active = None
         self._row_free = np.concatenate([self._row_free, np.ones(grow, dtype=bool)])
         self._n_free += grow
         self._srcmap_geom = None
@@ -408,6 +429,9 @@ class RolloutMonitor:
             self.anomalies = K.AnomalyBuffer(max(1024, 4 * cap), dev,
                                              count=self._rec_dev[cap * 4:cap * 4 + 1].view(torch.int32))
             self._graphs = {}
+            if self.mvn:  # a group has >= 2 rows: at most cap / 2 groups x Wc slots x 8 named metrics
+                self._mvn_anoms = K.AnomalyBuffer(max(1024, 4 * cap * self.Wc), dev)
+                self._mvn_out = {}
 
     def _free_rows(self, rows) -> None:
         ra = np.asarray(rows, dtype=np.int64)
@@ -420,6 +444,11 @@ class RolloutMonitor:
         self.row_job[ra] = -1
         self.row_k[ra] = -1
         self.biv_b[ra] = -1
+        if self.mvn:
+            self.mvn_rows.index_fill_(0, idx, -1)
+            self.mvn_k[ra] = 0
+            self.mvn_rows_h[ra] = -1
+            self._mvn_active = None
         self.model_ok[ra] = False
         self._fam_count(self.row_fam[ra], -1)
         self.row_fam[ra] = -1
@@ -506,7 +535,7 @@ class RolloutMonitor:
 
     def _claimable_many(self, docs) -> List[bool]:
         """Claim filter over a batch: one native decode for every unseen document."""
-        plans = pl.plan_many(docs, self.cfg.algorithm, self.step, self.Wc)
+        plans = pl.plan_many(docs, self.cfg.algorithm, self.step, self.Wc, joint_served=self._served)
         if self.owns is None:
             return [p is not None for p in plans]
         if self.router is not None and self.owns == self.owns_affine:
@@ -520,7 +549,7 @@ class RolloutMonitor:
         docs = self.store.claim(self.worker_id, now=now, max_stuck_s=self.cfg.max_stuck_seconds,
                                 limit=self.claim_limit, only_batch=self._claimable_many, steal_from=steal_from)
         t1 = time.perf_counter()
-        plans = pl.plan_many(docs, self.cfg.algorithm, self.step, self.Wc)
+        plans = pl.plan_many(docs, self.cfg.algorithm, self.step, self.Wc, joint_served=self._served)
         hist = self.history
         n = 0
         groups: Dict[int, Tuple[PlanCols, List[RolloutPlan]]] = {}
@@ -750,7 +779,9 @@ class RolloutMonitor:
         """Joint models of the admitted multi-metric jobs (``ML_ALGORITHM`` bivariate_normal
         / auto): the bivariate normal of a job's first two aliases (sorted, as
         ``brain/worker.py`` pairs them), fitted on their 7-day histories ending at the
-        job's start (K8 ``bivariate`` kernel on the GPU), kept on the first alias's row."""
+        job's start (K8 ``bivariate`` kernel on the GPU), kept on the first alias's row.
+        ``multivariate_normal`` with ``FOREMAST_ROLLOUT_MVN=1``: the k-variate normal of all
+        its aliases (:meth:`_fit_mvn`)."""
         algo = self.cfg.algorithm
         if algo not in pl.JOINT_ALGORITHMS:
             return
@@ -759,6 +790,7 @@ class RolloutMonitor:
         ia, ib = [], []   # batch rows of each bivariate job's two aliases
         now = self.clock()
         attach = []       # the joint LSTM's new entities, referenced in one call
+        mv = []           # batch rows of each k-variate job's aliases in sorted order
         for i, p in enumerate(b.plans):
             kind = pl.joint_kind(algo, p.n)
             if kind is None:
@@ -772,10 +804,19 @@ class RolloutMonitor:
                 attach.append((p.doc_id, [al[k] for k in order], p.cols.u64[p.s0 + np.asarray(order), 0].tolist(),
                                p.app, p.end_ts, lambda i, p=p, order=order: p.cols.hkey_at(p.s0 + order[i])))
                 continue
+            if kind == "mvn":
+                if len(order) > mvn_ref.MAX_K:
+                    log.warning("job %s has %d metrics: multivariate_normal models the first %d (%s)",
+                                p.doc_id, len(order), mvn_ref.MAX_K, ",".join(al[k] for k in order[:mvn_ref.MAX_K]))
+                    order = order[:mvn_ref.MAX_K]
+                mv.append(starts[i] + np.asarray(order, dtype=np.int64))
+                continue
             ia.append(starts[i] + order[0])
             ib.append(starts[i] + order[1])
         if attach:
             self.joint_lstm.attach_many(attach, now)
+        if mv:
+            self._fit_mvn(b, mv)
         if not ia:
             return
         ia, ib = np.asarray(ia, dtype=np.int64), np.asarray(ib, dtype=np.int64)
@@ -806,10 +847,101 @@ class RolloutMonitor:
             self.biv_ok[ra] = count.to(dev) >= self.cfg.min_historical_points
         self.biv_b[b.rows[ia]] = b.rows[ib]
 
+    def _fit_mvn(self, b: "_Batch", mv: List[np.ndarray]) -> None:
+        """The k-variate normal of each job in ``mv`` (batch rows of its aliases in sorted
+        order, at most 8): fitted on the jointly valid points of the resident history ending
+        at the job's start, read in place (``mvn_fit_state``: every job's own window length in
+        one launch; CPU: ``fit_mvn`` + ``mvn_state``), kept on the first alias's row with the
+        group's window rows and ``thr2 = q_k(threshold of the first row)``."""
+        hist, dev, MK = self.history, self.device, mvn_ref.MAX_K
+        G = len(mv)
+        ks = np.fromiter((len(m) for m in mv), dtype=np.int64, count=G)
+        flat = np.concatenate(mv)
+        col = np.concatenate([np.arange(k) for k in ks.tolist()])
+        grp = np.repeat(np.arange(G), ks)
+        first = np.fromiter((m[0] for m in mv), dtype=np.int64, count=G)
+        htab = np.full((G, MK), -1, dtype=np.int64)
+        wtab = np.full((G, MK), -1, dtype=np.int64)
+        htab[grp, col] = hist.rows_of_h(b.u64[flat, 0].tolist())
+        wtab[grp, col] = b.rows[flat]
+        R = hist.R
+        drop = np.maximum(0, np.round((hist.t_last - b.f64[first, 2]) / self.step).astype(np.int64))
+        length = np.maximum(1, R - drop)
+        dst = b.rows[first]
+        # the raw threshold of the group's first row (BatchScorer.score_mvn), as _set_row_params stored it
+        thr2 = np.array([mvn_ref.chi2_threshold(float(np.float32(self._thr_cache[int(key)][0])), int(k))
+                         for key, k in zip(b.u64[first, 5].tolist(), ks.tolist())], dtype=np.float32)
+        ring = hist.ring
+        idx = torch.from_numpy(dst).to(dev)
+        if self.gpu:
+            from ..ops import kernels as K
+            state = {"mean": self.mvn_mean, "cov": self.mvn_cov, "chol": self.mvn_chol, "nvalid": self.mvn_nvalid}
+            K.mvn_fit_state(ring.data, ring.head, htab, length, dst, state)
+        else:
+            for k, ln in {(int(k), int(ln)) for k, ln in zip(ks, length)}:
+                sel = np.nonzero((ks == k) & (length == ln))[0]
+                t = (torch.arange(ln) + ring.head) % R
+                h = ring.data[torch.from_numpy(htab[sel, :k].reshape(-1))].index_select(1, t)
+                fit = mvn_ref.fit_mvn(h.view(len(sel), k, ln).permute(0, 2, 1).float())
+                at = idx[torch.from_numpy(sel)]
+                self.mvn_mean[at] = 0.0
+                self.mvn_cov[at] = 0.0
+                self.mvn_mean[at[:, None], torch.arange(k)[None, :]] = fit.mean.float()
+                self.mvn_cov[at[:, None], torch.arange(fit.cov.shape[1])[None, :]] = fit.cov.float()
+                self.mvn_chol[at] = mvn_ref.mvn_state(fit).float()
+                self.mvn_nvalid[at] = fit.count.float()
+        self.mvn_thr2[idx] = torch.from_numpy(thr2).to(dev)
+        self.mvn_rows[idx] = torch.from_numpy(wtab.astype(np.int32)).to(dev)
+        self.mvn_k[dst] = ks
+        self.mvn_rows_h[dst] = wtab
+        self._mvn_active = None
+
+    def _score_mvn(self):
+        """The live k-variate groups' points this tick: (row of a named metric, window slot,
+        that metric's pod mean) per anomalous slot (``d² > thr2`` with a model of enough
+        points) and named metric.  GPU: ``mvn_state_detect``, launched outside the captured
+        tick graph, then the K9 count (and, when non-zero, the list) copied back."""
+        live = np.nonzero(self.mvn_k > 0)[0]
+        if not len(live):
+            return None
+        P, Wc, min_valid = self.P, self.Wc, self.cfg.min_historical_points
+        if self.gpu:
+            from ..ops import kernels as K
+            if self._mvn_active is None:
+                kmask = 0
+                for k in np.unique(self.mvn_k[live]).tolist():
+                    kmask |= 1 << int(k)
+                self._mvn_active = (torch.from_numpy(live.astype(np.int32)).to(self.device), kmask)
+            active, kmask = self._mvn_active
+            ab = self._mvn_anoms
+            ab.reset()
+            state = {"mean": self.mvn_mean, "chol": self.mvn_chol, "nvalid": self.mvn_nvalid}
+            K.mvn_state_detect(state, self.mvn_rows, self.mvn_thr2, active, self.win, P, Wc, min_valid=min_valid,
+                               anomalies=ab, kmask=kmask, out=self._mvn_out)
+            rows, cols, vals, _over = ab.fetch()
+            return rows.astype(np.int64), cols.astype(np.int64), vals
+        out_r, out_c, out_v = [], [], []
+        ks = self.mvn_k[live]
+        for k in np.unique(ks).tolist():
+            sel = live[ks == k]
+            wr = self.mvn_rows_h[sel, :k]
+            at = torch.from_numpy(sel)
+            x = torch.nanmean(self.win[torch.from_numpy(wr.reshape(-1))].view(len(sel), k, P, Wc), 2).permute(0, 2, 1)
+            s = mvn_ref.score_state(self.mvn_mean[at][:, :k], self.mvn_chol[at], self.mvn_nvalid[at], x,
+                                    self.mvn_thr2[at], min_valid)
+            g, c, i = np.nonzero(s.names.numpy())
+            out_r.append(wr[g, i])
+            out_c.append(c)
+            out_v.append(x.numpy()[g, c, i])
+        return np.concatenate(out_r), np.concatenate(out_c), np.concatenate(out_v)
+
     def _score_joint(self):
         """Bivariate jobs' points this tick: (first-alias rows, window columns, pod-mean
         values) where the squared Mahalanobis distance of the two aliases' pod-mean
-        current values exceeds threshold^2 (``brain/batch.py`` ``score_bivariate``)."""
+        current values exceeds threshold^2 (``brain/batch.py`` ``score_bivariate``).
+        With the k-variate state tables (``self.mvn``): :meth:`_score_mvn`."""
+        if self.mvn:
+            return self._score_mvn()
         rows = np.nonzero(self.biv_b >= 0)[0]
         if not len(rows):
             return None

@@ -121,6 +121,8 @@ def brain(gpus: int = 8) -> List[Dict[str, Any]]:
             {"name": "FOREMAST_DTYPE", "value": "bf16"},
             # 1: a job the joint LSTM flags names only the metrics its verdict is blamed on
             {"name": "FOREMAST_LSTM_ATTRIBUTION", "value": "0"},
+            # 1: multi-metric rollout jobs under ML_ALGORITHM=multivariate_normal run on the resident engine
+            {"name": "FOREMAST_ROLLOUT_MVN", "value": "0"},
             # resident engines: continuous (streaming) + canary / rollingUpdate (rollout) jobs on the GPUs
             {"name": "FOREMAST_STREAMING", "value": "1"}, {"name": "FOREMAST_ROLLOUT", "value": "1"},
             # "reference": the reference brain's per-point thresholds (no window correction, one point

@@ -87,12 +87,11 @@ def cholesky_packed(cov: torch.Tensor, k: int, eps: float) -> Tuple[list, list]:
     return L, inv
 
 
-def _solve(fit: MvnFit, x: torch.Tensor, eps: float, want_contrib: bool):
-    dt = _promoted(fit, x)
-    k = fit.k
-    x = x.to(dt)
-    mean, cov = fit.mean.to(dt), fit.cov.to(dt)
-    L, inv = cholesky_packed(cov, k, eps)
+def _solve_factor(mean: torch.Tensor, L: list, inv: list, x: torch.Tensor, want_contrib: bool):
+    """The two triangular solves of a point block ``x [G, C, k]`` against the factor
+    (``L[i][j]``, ``inv[i] = 1 / L[i][i]``, lists of ``[G]`` tensors): ``d2 [G, C]`` and, when
+    wanted, the contributions ``[G, C, k]``; NaN where a coordinate is missing."""
+    k = x.shape[2]
     d = [x[..., i] - mean[:, None, i] for i in range(k)]
     z = []
     for i in range(k):   # z = L^-1 (x - mean)
@@ -115,6 +114,14 @@ def _solve(fit: MvnFit, x: torch.Tensor, eps: float, want_contrib: bool):
         w[i] = s * inv[i][:, None]
     c = torch.stack([d[i] * w[i] for i in range(k)], 2)
     return d2, torch.where(missing[..., None], torch.full_like(c, float("nan")), c)
+
+
+def _solve(fit: MvnFit, x: torch.Tensor, eps: float, want_contrib: bool):
+    dt = _promoted(fit, x)
+    x = x.to(dt)
+    mean, cov = fit.mean.to(dt), fit.cov.to(dt)
+    L, inv = cholesky_packed(cov, fit.k, eps)
+    return _solve_factor(mean, L, inv, x, want_contrib)
 
 
 def mahalanobis2_mvn(fit: MvnFit, x: torch.Tensor, eps: float = 1e-9) -> torch.Tensor:
@@ -182,16 +189,57 @@ class MvnScore:
     blame: torch.Tensor    # [G] int32 bit mask of the named metrics
 
 
+def _verdict(d2, c, count, thr2, min_valid: int) -> MvnScore:
+    k = c.shape[2]
+    ok = count >= min_valid
+    valid = ~torch.isnan(d2)
+    flag = valid & ok[:, None] & (d2 > thr2.to(d2.dtype)[:, None])
+    names = named(c, d2) & flag[..., None]
+    n = flag.sum(1).int()
+    verdict = torch.where(n > 0, 1, torch.where(valid.any(1) & ok, 0, -1)).to(torch.int8)
+    bits = (1 << torch.arange(k)).int().to(d2.device)
+    blame = (names.any(1).int() * bits).sum(1).int()
+    return MvnScore(d2=d2, contrib=c, flag=flag, names=names, count=n, verdict=verdict, blame=blame)
+
+
 def score_mvn(fit: MvnFit, x: torch.Tensor, thr2: torch.Tensor, min_valid: int, eps: float = 1e-9) -> MvnScore:
     """The verdict and attribution rules: a slot is anomalous iff the model is ok (jointly
     valid points >= ``min_valid``) and ``d² > thr2`` (``thr2 [G]`` = ``q_k(thr)``)."""
     d2, c = _solve(fit, x, eps, True)
-    ok = fit.count >= min_valid
-    valid = ~torch.isnan(d2)
-    flag = valid & ok[:, None] & (d2 > thr2.to(d2.dtype)[:, None])
-    names = named(c, d2) & flag[..., None]
-    count = flag.sum(1).int()
-    verdict = torch.where(count > 0, 1, torch.where(valid.any(1) & ok, 0, -1)).to(torch.int8)
-    bits = (1 << torch.arange(fit.k)).int()
-    blame = (names.any(1).int() * bits).sum(1).int()
-    return MvnScore(d2=d2, contrib=c, flag=flag, names=names, count=count, verdict=verdict, blame=blame)
+    return _verdict(d2, c, fit.count, thr2, min_valid)
+
+
+STATE_TRI = MAX_K * (MAX_K + 1) // 2   # 36: a state row holds the packed factor of an 8 x 8 matrix
+
+
+def mvn_state(fit: MvnFit, eps: float = 1e-9) -> torch.Tensor:
+    """The scoring state of a fit: ``chol [G, 36]`` packed like ``cov``.  Entries below the
+    diagonal hold ``L[i][j]``, diagonal slots hold ``1 / L[i][i]`` (``L Lᵀ = Σ + eps·I``, the
+    factor and pivot floor of ``cholesky_packed``), unused entries are 0.  With ``mean`` and
+    ``count`` it is all ``score_state`` needs: the fit is made once, the state scored every
+    tick (``ops/csrc/mvn_state.hip``)."""
+    k = fit.k
+    dt = torch.promote_types(torch.promote_types(fit.mean.dtype, fit.cov.dtype), torch.float32)
+    L, inv = cholesky_packed(fit.cov.to(dt), k, eps)
+    chol = torch.zeros((fit.cov.shape[0], STATE_TRI), dtype=dt, device=fit.cov.device)
+    for i in range(k):
+        for j in range(i):
+            chol[:, tri_index(i, j)] = L[i][j]
+        chol[:, tri_index(i, i)] = inv[i]
+    return chol
+
+
+def score_state(mean: torch.Tensor, chol: torch.Tensor, count: torch.Tensor, x: torch.Tensor, thr2: torch.Tensor,
+                min_valid: int) -> MvnScore:
+    """``score_mvn`` from the state: ``mean [G, >= k]``, ``chol [G, 36]`` (``mvn_state``),
+    ``count [G]`` and the points ``x [G, C, k]``.  The same solves, ``named`` rule, verdict and
+    blame; only the factorisation is not repeated."""
+    k = x.shape[2]
+    if not 2 <= k <= MAX_K:
+        raise ValueError(f"score_state takes 2..{MAX_K} metrics, got {k}")
+    dt = torch.promote_types(torch.promote_types(mean.dtype, chol.dtype), torch.promote_types(x.dtype, torch.float32))
+    mean, chol, x = mean.to(dt), chol.to(dt), x.to(dt)
+    L = [[chol[:, tri_index(i, j)] if j < i else None for j in range(k)] for i in range(k)]
+    inv = [chol[:, tri_index(i, i)] for i in range(k)]
+    d2, c = _solve_factor(mean, L, inv, x, True)
+    return _verdict(d2, c, count, thr2, min_valid)

@@ -11,6 +11,8 @@ K5/K11      ``rank_tests``                models/pairwise.py
 K6/K7       ``lstm_*``                    models/lstm_ae.py
 K8          ``bivariate``                 models/bivariate.py
 K8 (k <= 8) ``mvn_groups``                models/multivariate_normal.py
+K8 (state)  ``mvn_fit_state``             models/multivariate_normal.py (mvn_state)
+K8 (state)  ``mvn_state_detect``          models/multivariate_normal.py
 K9          fused detection epilogue      models/detect.py
 K10         ``ring_append``               ingest/ringbuffer.py
 ==========  ============================  ==========================================

@@ -106,6 +106,23 @@ class MvnGroupArgs(C.Structure):
     ]
 
 
+class MvnFitStateArgs(C.Structure):
+    _fields_ = [
+        ("hist", P), ("ld", LL), ("ring_len", I), ("head", I), ("N", I), ("Ng", I),
+        ("groups", P), ("len", P), ("dst", P), ("S", I), ("eps", F),
+        ("mean", P), ("cov", P), ("chol", P), ("nvalid", P), ("kmask", I), ("_pad", I),
+    ]
+
+
+class MvnStateDetectArgs(C.Structure):
+    _fields_ = [
+        ("mean", P), ("chol", P), ("nvalid", P), ("thr2", P), ("groups", P), ("S", I), ("Ng", I),
+        ("active", P), ("cur", P), ("ld_cur", LL), ("N", I), ("P", I), ("W", I), ("min_valid", I),
+        ("d2", P), ("count", P), ("verdict", P), ("score", P), ("blame", P), ("contrib", P),
+        ("anom_count", P), ("anom_series", P), ("anom_col", P), ("anom_val", P), ("anom_cap", I), ("kmask", I),
+    ]
+
+
 class LstmArgs(C.Structure):
     pass  # populated in lstm bindings (see kernels.py)
 
@@ -164,6 +181,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.fm_bivariate_pairs.restype = I
     lib.fm_mvn_groups.argtypes = [C.POINTER(MvnGroupArgs), I, P]
     lib.fm_mvn_groups.restype = I
+    lib.fm_mvn_fit_state.argtypes = [C.POINTER(MvnFitStateArgs), I, P]
+    lib.fm_mvn_fit_state.restype = I
+    lib.fm_mvn_state_detect.argtypes = [C.POINTER(MvnStateDetectArgs), P]
+    lib.fm_mvn_state_detect.restype = I
     lib.fm_ring_append.argtypes = [P, LL, I, I, I, P, LL, LL, I, P]
     lib.fm_ring_append.restype = I
     lib.fm_ring_append_dev.argtypes = [P, LL, I, I, P, I, P, LL, LL, I, P]

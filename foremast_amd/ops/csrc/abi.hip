@@ -12,6 +12,8 @@ extern "C" long long fm_abi_sizeof(const char* name) {
   if (!__builtin_strcmp(name, "BivArgs")) return sizeof(BivArgs);
   if (!__builtin_strcmp(name, "BivPairArgs")) return sizeof(BivPairArgs);
   if (!__builtin_strcmp(name, "MvnGroupArgs")) return sizeof(MvnGroupArgs);
+  if (!__builtin_strcmp(name, "MvnFitStateArgs")) return sizeof(MvnFitStateArgs);
+  if (!__builtin_strcmp(name, "MvnStateDetectArgs")) return sizeof(MvnStateDetectArgs);
   return -1;
 }
 
@@ -26,5 +28,7 @@ extern "C" long long fm_abi_offsetof(const char* name, const char* field) {
   if (!__builtin_strcmp(name, "BivArgs")) { FM_OFF(BivArgs, eps); FM_OFF(BivArgs, app_stats); }
   if (!__builtin_strcmp(name, "BivPairArgs")) { FM_OFF(BivPairArgs, threshold); FM_OFF(BivPairArgs, anom_val); }
   if (!__builtin_strcmp(name, "MvnGroupArgs")) { FM_OFF(MvnGroupArgs, thr2); FM_OFF(MvnGroupArgs, contrib); FM_OFF(MvnGroupArgs, anom_val); FM_OFF(MvnGroupArgs, kmask); }
+  if (!__builtin_strcmp(name, "MvnFitStateArgs")) { FM_OFF(MvnFitStateArgs, groups); FM_OFF(MvnFitStateArgs, dst); FM_OFF(MvnFitStateArgs, eps); FM_OFF(MvnFitStateArgs, chol); FM_OFF(MvnFitStateArgs, kmask); }
+  if (!__builtin_strcmp(name, "MvnStateDetectArgs")) { FM_OFF(MvnStateDetectArgs, active); FM_OFF(MvnStateDetectArgs, ld_cur); FM_OFF(MvnStateDetectArgs, min_valid); FM_OFF(MvnStateDetectArgs, contrib); FM_OFF(MvnStateDetectArgs, anom_cap); FM_OFF(MvnStateDetectArgs, kmask); }
   return -1;
 }

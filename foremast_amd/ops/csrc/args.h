@@ -240,3 +240,58 @@ struct MvnGroupArgs {
   int kmask;              // bit k: some group may have k rows (0: unknown, every k is launched)
   int _pad;
 };
+
+// The k-variate normal as a resident state (rollout engine): fitted once per job at admission
+// (fm_mvn_fit_state), scored every tick against the window table (fm_mvn_state_detect).  The
+// state tables have S rows; a job's state lives at the row of its first alias.
+//   mean [S, 8], cov [S, 36] as MvnGroupArgs; chol [S, 36] packed like cov: entries below the
+//   diagonal hold L[i][j], diagonal slots hold 1 / L[i][i] (L L^T = cov + eps I), unused 0.
+struct MvnFitStateArgs {
+  const void* hist;       // [N, ld] ring (float or bf16), read in place
+  long long ld;
+  int ring_len;
+  int head;
+  int N;
+  int Ng;
+  const int* groups;      // [Ng, 8] ring rows padded with -1
+  const int* len;         // [Ng] logical window [head, head + len) of each group
+  const int* dst;         // [Ng] state row each group writes (outside [0, S): nothing written)
+  int S;
+  float eps;
+  float* mean;            // [S, 8]
+  float* cov;             // [S, 36]
+  float* chol;            // [S, 36]
+  float* nvalid;          // [S]
+  int kmask;              // as MvnGroupArgs
+  int _pad;
+};
+
+struct MvnStateDetectArgs {
+  const float* mean;      // [S, 8]
+  const float* chol;      // [S, 36]
+  const float* nvalid;    // [S]
+  const float* thr2;      // [S] q_k(thr) of the group
+  const int* groups;      // [S, 8] rows of cur padded with -1
+  int S;
+  int Ng;
+  const int* active;      // [Ng] live state rows
+  const float* cur;       // [N, ld_cur] window table, column p * W + slot
+  long long ld_cur;
+  int N;
+  int P;
+  int W;
+  int min_valid;
+  float* d2;              // [Ng, W]
+  int* count;             // [Ng]
+  signed char* verdict;   // [Ng]
+  float* score;           // [Ng] max d
+  int* blame;             // [Ng]
+  float* contrib;         // [Ng, W, 8] or null
+  // K9 compaction (optional): (window row of a named metric, slot, pod mean of that metric)
+  int* anom_count;
+  int* anom_series;
+  int* anom_col;
+  float* anom_val;
+  int anom_cap;
+  int kmask;
+};

@@ -22,119 +22,17 @@
 // each row once in the per-app table (groups may share a row: the first to exchange
 // raised[row] does it), and appends (row, slot, pod mean) per anomalous slot and named
 // metric to the K9 list.
-#include "common.h"
-#include "args.h"
+#include "mvn_common.h"
 
 #ifndef FM_MVN_WAVES
 #define FM_MVN_WAVES 4   // groups (waves) per workgroup
 #endif
 constexpr int kMvnBlock = FM_MVN_WAVES * FM_WAVE;
-constexpr float kMvnPivotFloor = 1e-20f;
-
-#define MVN_TRI(i, j) ((i) * ((i) + 1) / 2 + (j))   // i >= j
-
-template <int K>
-struct MvnAcc {
-  static constexpr int TRI = K * (K + 1) / 2;
-  float s[K], a[K], p[TRI];
-  float c = 0.f;
-  bool has = false;
-  __device__ __forceinline__ MvnAcc() {
-#pragma unroll
-    for (int i = 0; i < K; ++i) { s[i] = 0.f; a[i] = 0.f; }
-#pragma unroll
-    for (int i = 0; i < TRI; ++i) p[i] = 0.f;
-  }
-  __device__ __forceinline__ void add(const float (&x)[K]) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < K; ++i) ok = ok && (x[i] == x[i]);
-    // branch-free: a point with a missing coordinate adds exact zeros; the first jointly
-    // valid point of the lane becomes its shift
-    const bool first = ok && !has;
-    has = has || ok;
-    float d[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-      s[i] = first ? x[i] : s[i];
-      d[i] = ok ? x[i] - s[i] : 0.f;
-      a[i] += d[i];
-    }
-    c += ok ? 1.f : 0.f;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-#pragma unroll
-      for (int j = 0; j <= i; ++j) p[MVN_TRI(i, j)] += d[i] * d[j];
-    }
-  }
-};
-
-// Physical columns [0, R) of the K rows: 16-byte loads, UNR per row in flight (clamped index,
-// no branch before the loads), scalar tail of R % VEC columns.
-template <typename TIN, int K, int UNR>
-__device__ __forceinline__ void mvn_acc_full(const TIN* const (&row)[K], int R, int lane, MvnAcc<K>& s) {
-  constexpr int VEC = 16 / sizeof(TIN);
-  const int nvec = R / VEC;
-  for (int v0 = lane; v0 < nvec; v0 += FM_WAVE * UNR) {
-    uint4 q[UNR][K];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int v = min(v0 + u * FM_WAVE, nvec - 1);
-#pragma unroll
-      for (int i = 0; i < K; ++i) q[u][i] = *(const uint4*)(row[i] + (long long)v * VEC);
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      if (v0 + u * FM_WAVE >= nvec) break;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        unsigned word[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) word[i] = w == 0 ? q[u][i].x : (w == 1 ? q[u][i].y : (w == 2 ? q[u][i].z : q[u][i].w));
-        float x[K];
-        if (sizeof(TIN) == 2) {
-#pragma unroll
-          for (int i = 0; i < K; ++i) x[i] = __uint_as_float(word[i] << 16);
-          s.add(x);
-#pragma unroll
-          for (int i = 0; i < K; ++i) x[i] = __uint_as_float(word[i] & 0xffff0000u);
-          s.add(x);
-        } else {
-#pragma unroll
-          for (int i = 0; i < K; ++i) x[i] = __uint_as_float(word[i]);
-          s.add(x);
-        }
-      }
-    }
-  }
-  for (int t = nvec * VEC + lane; t < R; t += FM_WAVE) {
-    float x[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) x[i] = to_f32<TIN>(row[i][t]);
-    s.add(x);
-  }
-}
-
-__device__ __forceinline__ int wave_or(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, FM_WAVE);
-  return v;
-}
-
-// leading non-negative entries of a group's row table
-__device__ __forceinline__ int mvn_group_k(const int* g) {
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < FM_MVN_MAXK; ++i) {
-    if (k == i && g[i] >= 0) k = i + 1;
-  }
-  return k;
-}
 
 template <typename TIN, bool FULL, int K>
 __global__ __launch_bounds__(kMvnBlock) void mvn_groups_kernel(const MvnGroupArgs a, const int kfirst) {
   constexpr int TRI = K * (K + 1) / 2;
-  constexpr int UNR = K <= 2 ? 5 : (K == 3 ? 3 : (K <= 5 ? 2 : 1));
+  constexpr int UNR = MvnUnroll<K>::value;
   const int q = blockIdx.x * FM_MVN_WAVES + wave_id();
   if (q >= a.Ng) return;  // wave-uniform
   const int lane = lane_id();
@@ -167,39 +65,10 @@ __global__ __launch_bounds__(kMvnBlock) void mvn_groups_kernel(const MvnGroupArg
   if (FULL) {
     mvn_acc_full<TIN, K, UNR>(row, a.ring_len, lane, s);
   } else {
-    for (int t = lane; t < a.len; t += FM_WAVE) {
-      int p = a.head + t;
-      if (p >= a.ring_len) p -= a.ring_len;
-      float x[K];
-#pragma unroll
-      for (int i = 0; i < K; ++i) x[i] = to_f32<TIN>(row[i][p]);
-      s.add(x);
-    }
+    mvn_acc_wrapped<TIN, K>(row, a.ring_len, a.head, a.len, lane, s);
   }
-  // per-lane centred moments, merged about a wave-common centre (see bivariate.hip)
-  const float c = s.c;
-  const float rc = c > 0.f ? 1.f / c : 0.f;
-  const float N = wave_sum(c);
-  const float rN = N > 0.f ? 1.f / N : 0.f;
-  float mean[K], dm[K];
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    const float m0 = wave_sum(c > 0.f ? c * (s.s[i] + s.a[i] * rc) : 0.f) * rN;
-    const float u_t = c > 0.f ? (s.s[i] - m0) + s.a[i] * rc : 0.f;
-    const float u = wave_sum(c * u_t) * rN;
-    mean[i] = m0 + u;
-    dm[i] = u_t - u;
-  }
-  const float inv = 1.f / fmaxf(N, 1.f);
-  float v[TRI];
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-#pragma unroll
-    for (int j = 0; j <= i; ++j) {
-      const float cij = c > 0.f ? s.p[MVN_TRI(i, j)] - s.a[i] * s.a[j] * rc : 0.f;
-      v[MVN_TRI(i, j)] = wave_sum(cij + c * dm[i] * dm[j]) * inv;
-    }
-  }
+  float mean[K], v[TRI], N;
+  mvn_merge<K>(s, mean, v, N);
   if (lane == 0) {
 #pragma unroll
     for (int i = 0; i < FM_MVN_MAXK; ++i) a.mean[(long long)q * FM_MVN_MAXK + i] = i < K ? mean[i] : 0.f;
@@ -207,23 +76,8 @@ __global__ __launch_bounds__(kMvnBlock) void mvn_groups_kernel(const MvnGroupArg
     for (int i = 0; i < FM_MVN_TRI; ++i) a.cov[(long long)q * FM_MVN_TRI + i] = i < TRI ? v[i] : 0.f;
     a.nvalid[q] = N;
   }
-  // Cholesky factor of cov + eps I in place: v[(i, j)] = L[i][j] (j < i), il[i] = 1 / L[i][i]
   float il[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-#pragma unroll
-    for (int i = j; i < K; ++i) {
-      float t = v[MVN_TRI(i, j)] + (i == j ? a.eps : 0.f);
-#pragma unroll
-      for (int m = 0; m < j; ++m) t -= v[MVN_TRI(i, m)] * v[MVN_TRI(j, m)];
-      if (i == j) {
-        if (t < kMvnPivotFloor) t = kMvnPivotFloor;
-        il[j] = 1.f / sqrtf(t);
-      } else {
-        v[MVN_TRI(i, j)] = t * il[j];
-      }
-    }
-  }
+  mvn_cholesky<K>(v, il, a.eps);
   const float thr2 = a.thr2[q];
   const bool model_ok = N >= (float)a.min_valid;
   const float* cur[K];
@@ -233,72 +87,20 @@ __global__ __launch_bounds__(kMvnBlock) void mvn_groups_kernel(const MvnGroupArg
   int blame = 0;
   for (int slot = lane; slot < a.W; slot += FM_WAVE) {
     // pod means over the pods present in the slot (NaN: none)
-    float sp[K], np[K];
-#pragma unroll
-    for (int i = 0; i < K; ++i) { sp[i] = 0.f; np[i] = 0.f; }
-    for (int p = 0; p < a.P; ++p) {
-#pragma unroll
-      for (int i = 0; i < K; ++i) {
-        const float x = cur[i][p * a.W + slot];
-        if (x == x) { sp[i] += x; np[i] += 1.f; }
-      }
-    }
-    bool present = true;
-#pragma unroll
-    for (int i = 0; i < K; ++i) present = present && np[i] > 0.f;
-    float d2 = fm_nan();
     float x[K], ci[K];
+    const bool present = mvn_pod_means<K>(cur, a.P, a.W, slot, x);
+    float d2 = fm_nan();
 #pragma unroll
-    for (int i = 0; i < K; ++i) { x[i] = fm_nan(); ci[i] = fm_nan(); }
+    for (int i = 0; i < K; ++i) ci[i] = fm_nan();
     if (present) {
-      float d[K], z[K], w[K];
-#pragma unroll
-      for (int i = 0; i < K; ++i) { x[i] = sp[i] / np[i]; d[i] = x[i] - mean[i]; }
-      d2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < K; ++i) {   // z = L^-1 d
-        float t = d[i];
-#pragma unroll
-        for (int m = 0; m < i; ++m) t -= v[MVN_TRI(i, m)] * z[m];
-        z[i] = t * il[i];
-        d2 += z[i] * z[i];
-      }
-#pragma unroll
-      for (int i = K - 1; i >= 0; --i) {   // w = L^-T z
-        float t = z[i];
-#pragma unroll
-        for (int m = i + 1; m < K; ++m) t -= v[MVN_TRI(m, i)] * w[m];
-        w[i] = t * il[i];
-        ci[i] = d[i] * w[i];
-      }
+      d2 = mvn_solve<K>(x, mean, v, il, ci);
       anyv = 1.f;
       sc = fmaxf(sc, sqrtf(fmaxf(d2, 0.f)));
       if (model_ok && d2 > thr2) {
         cnt += 1.f;
-        const float line = d2 * (1.f / K);
-        int top = 0;
-        float best = ci[0];
-        int names = 0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-          if (i > 0 && ci[i] > best) { best = ci[i]; top = i; }
-          if (ci[i] >= line) names |= 1 << i;
-        }
-        names |= 1 << top;
+        const int names = mvn_names<K>(ci, d2);
         blame |= names;
-        if (a.anom_count) {
-#pragma unroll
-          for (int i = 0; i < K; ++i) {
-            if (names & (1 << i)) {
-              const int at = atomicAdd(a.anom_count, 1);
-              if (at < a.anom_cap) {
-                a.anom_series[at] = r[i];
-                a.anom_col[at] = slot;
-                a.anom_val[at] = x[i];
-              }
-            }
-          }
-        }
+        if (a.anom_count) mvn_append<K>(names, r, slot, x, a.anom_count, a.anom_cap, a.anom_series, a.anom_col, a.anom_val);
       }
     }
     a.d2[(long long)q * a.W + slot] = d2;

@@ -1051,6 +1051,167 @@ def mvn_groups(hist: torch.Tensor, head: int, length: int, groups, cur: torch.Te
     return out
 
 
+MVN_STATE = {"mean": MVN_MAXK, "cov": MVN_TRI, "chol": MVN_TRI, "nvalid": 0}   # state tables: inner size
+
+
+def mvn_state_tables(rows: int, device) -> Dict[str, torch.Tensor]:
+    """Zeroed state tables of ``rows`` rows for ``mvn_fit_state`` / ``mvn_state_detect``."""
+    return {k: torch.zeros((rows, w) if w else (rows,), dtype=torch.float32, device=device)
+            for k, w in MVN_STATE.items()}
+
+
+def _mvn_state_check(state: Dict[str, torch.Tensor], names, dev) -> int:
+    _need(all(k in state for k in names), f"state needs the tables {tuple(names)}")
+    S = state["mean"].shape[0]
+    for k in names:
+        t, w = state[k], MVN_STATE[k]
+        _need(tuple(t.shape) == ((S, w) if w else (S,)), f"state[{k!r}] must be [{S}{', %d' % w if w else ''}]")
+        _need(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev,
+              f"state[{k!r}] must be contiguous float32 on {dev}")
+    return S
+
+
+def _mvn_index(t, n: Optional[int], lo: int, hi: int, name: str, dev) -> torch.Tensor:
+    """An int32 ``[n]`` index vector on ``dev``.  A numpy array / CPU tensor / list is checked
+    against ``[lo, hi)`` here and copied; a GPU tensor is taken as it is (the kernels skip an
+    entry outside the range, they never follow it)."""
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        _need(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == dev,
+              f"{name} must be contiguous int32 [n] on {dev}")
+    else:
+        import numpy as np
+        h = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        _need(h.ndim == 1 and (h.size == 0 or h.dtype.kind in "iu"), f"{name} must be an integer vector")
+        _need(h.size == 0 or (int(h.min()) >= lo and int(h.max()) < hi), f"{name} outside [{lo}, {hi})")
+        t = torch.from_numpy(np.ascontiguousarray(h, dtype=np.int32)).to(dev)
+    _need(n is None or t.shape[0] == n, f"{name} must be [{n}], got {tuple(t.shape)}")
+    return t
+
+
+def _mvn_table(groups, dev, kmask: int):
+    """``groups`` as a contiguous int32 ``[n, 8]`` device table padded with -1 and the bit mask
+    of the group sizes (host tables: computed here; a GPU table keeps the caller's ``kmask``).
+    Rows are not range-checked: the state kernels report a group with a row outside its table
+    as unscored and read nothing."""
+    if not (isinstance(groups, torch.Tensor) and groups.is_cuda):
+        import numpy as np
+        if isinstance(groups, torch.Tensor):
+            groups = groups.numpy()
+        if not isinstance(groups, np.ndarray):
+            rows = [list(g) for g in groups]
+            _need(all(len(g) <= MVN_MAXK for g in rows), f"a group takes at most {MVN_MAXK} rows")
+            groups = np.array([g + [-1] * (MVN_MAXK - len(g)) for g in rows], dtype=np.int64).reshape(-1, MVN_MAXK)
+        _need(groups.ndim == 2 and groups.shape[1] <= MVN_MAXK and (groups.size == 0 or groups.dtype.kind in "iu"),
+              f"groups must be integer [n, <= {MVN_MAXK}]")
+        lead = np.cumprod(groups >= 0, axis=1).astype(bool)
+        table = np.full((groups.shape[0], MVN_MAXK), -1, dtype=np.int32)
+        table[:, :groups.shape[1]] = np.where(lead, groups, -1)
+        kmask = 0
+        for v in np.unique(lead.sum(1)).tolist():
+            kmask |= 1 << max(int(v), 2)
+        groups = torch.from_numpy(table).to(dev)
+    _need(groups.dim() == 2 and groups.shape[1] == MVN_MAXK and groups.dtype == torch.int32
+          and groups.is_contiguous() and groups.device == dev,
+          f"groups must be contiguous int32 [n, {MVN_MAXK}] on {dev}")
+    return groups, int(kmask)
+
+
+def mvn_fit_state(hist: torch.Tensor, head: int, groups, length, dst, state: Dict[str, torch.Tensor], *,
+                  eps: float = 1e-9, kmask: int = 0) -> Dict[str, torch.Tensor]:
+    """Fit the k-variate normal of row groups of a ring into state tables
+    (``mvn_state.hip`` ``fm_mvn_fit_state``, semantics ``models/multivariate_normal.py``
+    ``fit_mvn`` + ``mvn_state``).  ``hist``: the ``[N, R]`` ring, read in place (any row
+    stride); ``groups``: ``[Ng, 8]`` ring rows padded with -1; ``length``: the logical window
+    ``[head, head + length)`` of every group, an int or ``[Ng]``; ``dst``: the row of ``state``
+    (``mvn_state_tables``) each group writes: ``mean``, ``cov``, ``chol`` and ``nvalid``.  The
+    other rows of the tables are not touched.  No allocation or synchronisation when every
+    index argument is already an int32 GPU tensor."""
+    lib = nat.require()
+    _cuda(hist, "hist")
+    _need(hist.dim() == 2 and hist.dtype in (torch.float32, torch.bfloat16) and hist.stride(1) == 1,
+          "hist must be float32 or bfloat16 [N, R] with contiguous rows")
+    dev = hist.device
+    N, R = hist.shape
+    _need(hist.stride(0) >= R, "hist rows overlap")
+    _need(0 <= int(head) < R, f"head {head} out of [0, {R})")
+    S = _mvn_state_check(state, MVN_STATE, dev)
+    groups, kmask = _mvn_table(groups, dev, kmask)
+    Ng = groups.shape[0]
+    if isinstance(length, int):
+        _need(0 < length <= R, f"length {length} out of (0, {R}]")
+        length = torch.full((Ng,), length, dtype=torch.int32, device=dev)
+    length = _mvn_index(length, Ng, 1, R + 1, "length", dev)
+    dst = _mvn_index(dst, Ng, 0, S, "dst", dev)
+    if Ng == 0:
+        return state
+    a = nat.MvnFitStateArgs()
+    a.hist, a.ld, a.ring_len, a.head, a.N, a.Ng = nat.ptr(hist), hist.stride(0), R, int(head), N, Ng
+    a.groups, a.len, a.dst, a.S, a.eps = nat.ptr(groups), nat.ptr(length), nat.ptr(dst), S, float(eps)
+    for k_ in MVN_STATE:
+        setattr(a, k_, nat.ptr(state[k_]))
+    a.kmask = kmask
+    nat.check(lib.fm_mvn_fit_state(a, int(hist.dtype == torch.bfloat16), nat.stream_handle(dev)), "fm_mvn_fit_state")
+    return state
+
+
+def mvn_state_detect(state: Dict[str, torch.Tensor], groups, thr2: torch.Tensor, active, cur: torch.Tensor,
+                     pods: int, window: int, *, min_valid: int = 0, anomalies: Optional[AnomalyBuffer] = None,
+                     contrib: bool = False, kmask: int = 0,
+                     out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """Score the live groups of the state tables against a window table (``mvn_state.hip``
+    ``fm_mvn_state_detect``, semantics ``models/multivariate_normal.py`` ``score_state``).
+    ``state``: the tables ``mvn_fit_state`` wrote (``mean``, ``chol``, ``nvalid``); ``groups``:
+    ``[S, 8]`` rows of ``cur`` per state row, padded with -1; ``thr2 [S]``: ``q_k(thr)`` per
+    state row; ``active [Ng]``: the state rows to score; ``cur``: ``[N, pods * window]``,
+    column ``p * window + slot``.  Outputs per active group in ``out``: ``d2 [Ng, window]``,
+    ``count``, ``verdict``, ``score``, ``blame`` and, with ``contrib``, ``contrib [Ng, window,
+    8]``; ``anomalies`` receives (window row of a named metric, slot, its pod mean) per
+    anomalous slot and named metric."""
+    lib = nat.require()
+    _cuda(cur, "cur")
+    dev = cur.device
+    names = ("mean", "chol", "nvalid")
+    S = _mvn_state_check(state, names, dev)
+    P, W = int(pods), int(window)
+    _need(P >= 1 and W >= 1, "pods and window must be >= 1")
+    N = cur.shape[0]
+    _need(cur.dim() == 2 and cur.shape[1] == P * W, f"cur must be [N, {P * W}], got {tuple(cur.shape)}")
+    _need(cur.dtype == torch.float32 and cur.stride(1) == 1 and cur.stride(0) >= P * W,
+          "cur must be float32 with unit inner stride")
+    groups, kmask = _mvn_table(groups, dev, kmask)
+    _need(groups.shape[0] == S, f"groups must have one row per state row ({S})")
+    _vec(thr2, S, torch.float32, "thr2", dev)
+    active = _mvn_index(active, None, 0, S, "active", dev)
+    Ng = active.shape[0]
+    out = {} if out is None else out
+    shapes = {"d2": ((Ng, W), torch.float32), "count": ((Ng,), torch.int32), "verdict": ((Ng,), torch.int8),
+              "score": ((Ng,), torch.float32), "blame": ((Ng,), torch.int32)}
+    if contrib:
+        shapes["contrib"] = ((Ng, W, MVN_MAXK), torch.float32)
+    for k_, (shape, dt) in shapes.items():
+        if k_ not in out or tuple(out[k_].shape) != shape or out[k_].dtype != dt or out[k_].device != dev:
+            out[k_] = torch.empty(shape, dtype=dt, device=dev)
+        _need(out[k_].is_contiguous(), f"out[{k_!r}] must be contiguous")
+    if not contrib:
+        out.pop("contrib", None)
+    if Ng == 0 or N == 0:
+        return out
+    a = nat.MvnStateDetectArgs()
+    a.mean, a.chol, a.nvalid = nat.ptr(state["mean"]), nat.ptr(state["chol"]), nat.ptr(state["nvalid"])
+    a.thr2, a.groups, a.S, a.Ng, a.active = nat.ptr(thr2), nat.ptr(groups), S, Ng, nat.ptr(active)
+    a.cur, a.ld_cur, a.N, a.P, a.W, a.min_valid = nat.ptr(cur), cur.stride(0), N, P, W, int(min_valid)
+    for k_ in shapes:
+        setattr(a, k_, nat.ptr(out[k_]))
+    if anomalies is not None:
+        _need(anomalies.count.device == dev, "anomaly buffer on wrong device")
+        a.anom_count, a.anom_series, a.anom_col, a.anom_val = (nat.ptr(anomalies.count), nat.ptr(anomalies.series),
+                                                               nat.ptr(anomalies.col), nat.ptr(anomalies.val))
+        a.anom_cap = anomalies.cap
+    a.kmask = kmask
+    nat.check(lib.fm_mvn_state_detect(a, nat.stream_handle(dev)), "fm_mvn_state_detect")
+    return out
+
+
 def ring_append(dst: torch.Tensor, col0: int, src: torch.Tensor, col_dev: Optional[torch.Tensor] = None) -> None:
     """``dst[n, (col0 + j) % R] = src[n, j]`` (dst may be float32 or bf16); ``col_dev``
     (int32 device scalar): added to ``col0`` on the device (graph-captured ticks)."""

@@ -71,6 +71,10 @@ class BrainConfig:
     # resident LSTM engine: a flagged job names only the metrics its verdict is blamed on
     # (FOREMAST_LSTM_ATTRIBUTION = 0 | 1; docs/SCORING.md "Which metric broke"); off: every metric
     lstm_attribution: bool = False
+    # resident rollout engine: serve the multi-metric jobs of ML_ALGORITHM=multivariate_normal
+    # from a k x k state fitted at admission (FOREMAST_ROLLOUT_MVN = 0 | 1; docs/SCORING.md
+    # "multivariate_normal on the resident rollout engine"); off: they stay with BrainWorker
+    rollout_mvn: bool = False
     # downstream impact: joint model over each caller's metrics (ML_DOWNSTREAM_ALGORITHM lstm | none)
     downstream_algorithm: str = "lstm"
     # --- MI355X engine knobs -------------------------------------------------------
@@ -172,6 +176,10 @@ class BrainConfig:
         if attribution not in ("0", "1"):
             raise ValueError(f"FOREMAST_LSTM_ATTRIBUTION must be 0 or 1, not {attribution!r}")
         c.lstm_attribution = attribution == "1"
+        rollout_mvn = (e.get("FOREMAST_ROLLOUT_MVN") or "0").strip()
+        if rollout_mvn not in ("0", "1"):
+            raise ValueError(f"FOREMAST_ROLLOUT_MVN must be 0 or 1, not {rollout_mvn!r}")
+        c.rollout_mvn = rollout_mvn == "1"
         c.downstream_algorithm = (e.get("ML_DOWNSTREAM_ALGORITHM") or c.downstream_algorithm).strip().lower()
         c.dtype = (e.get("FOREMAST_DTYPE") or c.dtype).strip().lower()
         if c.dtype not in RING_DTYPES:
