@@ -177,6 +177,82 @@ def test_fp8_kernel_matches_emulated_fp8_reference(F):
     assert float(np.percentile(d_kernel.numpy(), 99.9)) < 0.25 * float(np.percentile(d_quant.numpy(), 99.9))
 
 
+def _bf16_ref():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "lstm_bf16_ref", os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "lstm_bf16_ref.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _score_bf16_against_model(m, x, ring=None):
+    """lstm_score (bf16) on buffers with sentinel rows behind row N, against the fp64 model that
+    rounds to bf16 where the kernel does (helpers/lstm_bf16_ref.py): recon and err within
+    0.1 (mean) / 0.25 (99.9th percentile) of the model's own quantisation gap."""
+    BR = _bf16_ref()
+    dev = torch.device("cuda:0")
+    N, T, F = x.shape
+    pad = 3
+    prm = BR.params_of(m)
+    rnd = BR.reference(prm, x, rounding=True, backward=False)
+    unr = BR.reference(prm, x, rounding=False, backward=False)
+    whole = {"err": torch.full((N + pad,), -12345.5, device=dev), "zscore": torch.full((N + pad,), -12345.5, device=dev),
+             "verdict": torch.full((N + pad,), 77, dtype=torch.int8, device=dev),
+             "recon": torch.full((N + pad, T, F), -12345.5, device=dev)}
+    out = {k: w[:N] for k, w in whole.items()}
+    mu, sigma = float(rnd["err"].mean()), float(rnd["err"].std(unbiased=False)) + 1e-3
+    p = L.pack(m, fp8=False, device=dev)
+    L.lstm_score(p, None if ring is not None else x.to(dev).contiguous(), mu=mu, sigma=sigma, thr_default=1.0,
+                 want_recon=True, out=out, ring=ring, T=T)
+    torch.cuda.synchronize()
+    for k, w in whole.items():
+        assert bool((w[N:] == (77 if k == "verdict" else -12345.5)).all()), f"{k}: rows behind row N were written"
+    got = {"y": out["recon"].double().cpu(), "err": out["err"].double().cpu()}
+    res = BR.measure(got, rnd, unr, names=("y", "err"), grads=False)
+    print(f"bf16 scoring N={N} T={T} F={F}: {BR.fmt(res)}")
+    assert res["y"]["gap_mean"] > 0 and res["err"]["gap_mean"] > 0     # the test can tell bf16 from fp32
+    assert not BR.violations(res), BR.violations(res)
+    z = (out["err"].cpu() - mu) / sigma
+    torch.testing.assert_close(out["zscore"].cpu(), z, rtol=1e-5, atol=1e-5)
+    clear = (z - 1.0).abs() > 1e-4
+    assert torch.equal(out["verdict"].cpu()[clear], (z > 1.0).to(torch.int8)[clear])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F", [1, 7])
+@pytest.mark.parametrize("T", [1, 2, 7, 24])
+@pytest.mark.parametrize("N", [1, 33, 129])
+def test_bf16_kernel_matches_emulated_bf16_reference(N, T, F):
+    """The bf16 twin of test_fp8_kernel_matches_emulated_fp8_reference: at the lane-half (1),
+    wave (33) and workgroup (129) edges, T from one step up, F at both ends (inputs at
+    k = 64..70, next to the bias at k = 71).  Measured on the MI355X, kernel to model over the
+    model's quantisation gap (mean / 99.9th percentile, bounds 0.1 / 0.25), largest over the
+    grid: recon 2.6e-2 (N = 33, T = 24, F = 1) / 1.2e-1 (N = 129, T = 24, F = 1), err 2.2e-2
+    (N = 33, T = 7, F = 7) / 1.5e-1 (N = 129, T = 7, F = 1); N = 1: <= 6.2e-3 on both."""
+    m, x = _bf16_ref().make_case(N, T, F)
+    _score_bf16_against_model(m, x)
+
+
+@pytest.mark.gpu
+def test_bf16_kernel_matches_emulated_bf16_reference_ring_input():
+    """The same, reading fp32 rings (row-padded storage) from a start column that wraps."""
+    dev = torch.device("cuda:0")
+    N, T, F, R = 33, 7, 7, 40
+    m, _ = _bf16_ref().make_case(N, T, F)
+    g = torch.Generator().manual_seed(17)
+    store = [torch.randn(N, 48, generator=g) * (f + 1) + f for f in range(F)]
+    mean = torch.stack([s[:, :R].mean(1) for s in store], 1).contiguous()
+    rstd = (1.0 / torch.stack([s[:, :R].std(1) for s in store], 1)).contiguous()
+    start = R - 3
+    cols = (start + torch.arange(T)) % R
+    x = torch.stack([s[:, :R][:, cols] for s in store], 2)
+    x = ((x - mean[:, None]) * rstd[:, None]).contiguous()
+    ring = L.RingSource(rings=[s.to(dev)[:, :R] for s in store], start_col=start, mean=mean.to(dev), rstd=rstd.to(dev))
+    _score_bf16_against_model(m, x, ring=ring)
+
+
 @pytest.mark.gpu
 def test_fp8_scoring_saturates_out_of_range_inputs():
     """A regressed window's z-scored inputs can exceed the fp8 e4m3 range
