@@ -157,6 +157,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.fm_hw_q_fit_dt.restype = I
     lib.fm_hw_d_split_plan.argtypes = [I, I, I]
     lib.fm_hw_d_split_plan.restype = I
+    # the pair table's lane-power section (B^0 .. B^15 per pair), filled once per table
+    lib.fm_hw_lane_powers.argtypes = [P, I, I, P]
+    lib.fm_hw_lane_powers.restype = I
     lib.fm_es_seq_fit.argtypes = [C.POINTER(SmoothArgs), I, I, P]
     lib.fm_es_seq_fit.restype = I
     lib.fm_es_seq_tpc.argtypes = [I]

@@ -200,11 +200,14 @@ __device__ __forceinline__ void pass2(const Y& y, const Y& yn, V* s, V c1, V c2,
 //   [6+4K .. +40)     B^1, B^2, B^4, B^8, B^16 (B = A^K), each m11 m12 m21 m22
 // so pass 1 is  v = sum_i W_i u_i  (3 ops/step) and the cross-lane scan only
 // carries the state vector with wave-uniform matrices.
+// (the layout as functions of K: the table's fill kernel takes K at run time)
+constexpr int pair_tab_b0(int K) { return 6 + 4 * K; }
+constexpr int pair_tab_size(int K) { return ((pair_tab_b0(K) + 40) + 15) / 16 * 16; }
 template <int K>
 struct PairTab {
   static constexpr int W0 = 6;
-  static constexpr int B0 = 6 + 4 * K;
-  static constexpr int SIZE = ((B0 + 40) + 15) / 16 * 16;
+  static constexpr int B0 = pair_tab_b0(K);
+  static constexpr int SIZE = pair_tab_size(K);
 };
 
 __device__ __forceinline__ v2f ldv2(const float* p) { return *(const v2f*)p; }
@@ -1544,6 +1547,68 @@ __device__ __forceinline__ void d_means(const DLds<K, S>& L, int m, int ns1, int
   });
 }
 
+// B^j (j = 0 .. 15) from B^1, B^2, B^4, B^8, by the bits of j from the lowest: the lane
+// scans' Bj = B^(lane & 15).  Each a * b + c * d is spelled fma(a, b, c * d): the second
+// product rounded, the first fused onto it.  That is how -ffp-contract=fast contracted
+// matmul(Bj, Bp[bit]) in every hw_d_kernel / hw_q_kernel instantiation while each wave built
+// its own Bj (and still does in hw_dg_block), so the table holds the bits the walks had.
+__device__ __forceinline__ v2f fma2(v2f x, v2f y, v2f z) {
+  v2f r;
+  r.x = __builtin_fmaf(x.x, y.x, z.x);
+  r.y = __builtin_fmaf(x.y, y.y, z.y);
+  return r;
+}
+__device__ __forceinline__ Mat2 lane_power(const Mat2* Bp, int j) {
+  const v2f one = splat2(1.f), zero = splat2(0.f);
+  Mat2 Bj;
+  Bj.a = one; Bj.b = zero; Bj.c = zero; Bj.d = one;
+#pragma unroll
+  for (int bit = 0; bit < 4; ++bit) {
+    const Mat2& q = Bp[bit];
+    Mat2 r;
+    r.a = fma2(Bj.a, q.a, Bj.b * q.c); r.b = fma2(Bj.a, q.b, Bj.b * q.d);
+    r.c = fma2(Bj.c, q.a, Bj.d * q.c); r.d = fma2(Bj.c, q.b, Bj.d * q.d);
+    if ((j >> bit) & 1) Bj = r;
+  }
+  return Bj;
+}
+
+// The lane-power section of the pair table: [npairs][16][8] floats after the PairTab rows and
+// the gapped kernel's [npairs][K + 1][8] powers of A; entry j of a pair is B^j (a Mat2 of v2f).
+// Filled once per grid on the device (hw_lane_powers_kernel) from the table's own fp32 B^1,
+// B^2, B^4, B^8: it depends on (alpha, beta) and the lane only, and building it per grid pair
+// in every wave of every block cost 52 vector instructions a pair (docs/PERF.md, "Per-pair
+// set-up").
+template <int K>
+__device__ __forceinline__ const float* lane_powers(const SmoothArgs& a, int pi) {
+  const size_t npairs = (size_t)((a.G + 1) / 2);
+  return a.pair_tab + npairs * (PairTab<K>::SIZE + 8 * (K + 1)) + (size_t)pi * 128;
+}
+
+// One thread per (pair, j); K at run time: a table is built for any K, by any caller.
+__global__ __launch_bounds__(256) void hw_lane_powers_kernel(float* tab, int npairs, int K) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 16 * npairs) return;
+  const int pi = i >> 4, j = i & 15;
+  const float* tb = tab + (size_t)pi * pair_tab_size(K) + pair_tab_b0(K);
+  Mat2 Bp[4];
+#pragma unroll
+  for (int bit = 0; bit < 4; ++bit) Bp[bit] = ldmat(tb + 8 * bit);
+  const Mat2 m = lane_power(Bp, j);
+  float* o = tab + (size_t)npairs * (pair_tab_size(K) + 8 * (K + 1)) + (size_t)i * 8;
+  o[0] = m.a.x; o[1] = m.a.y; o[2] = m.b.x; o[3] = m.b.y;
+  o[4] = m.c.x; o[5] = m.c.y; o[6] = m.d.x; o[7] = m.d.y;
+}
+
+// Fills the lane-power section of `tab`, a pair table of `npairs` pairs at K with its first
+// two sections in place and 128 more floats per pair after them.  Once per table.
+extern "C" int fm_hw_lane_powers(float* tab, int npairs, int K, hipStream_t st) {
+  if (!tab || npairs < 0 || K < 1) return (int)hipErrorInvalidValue;
+  if (npairs == 0) return 0;
+  hipLaunchKernelGGL(hw_lane_powers_kernel, dim3((16 * npairs + 255) / 256), dim3(256), 0, st, tab, npairs, K);
+  return (int)hipGetLastError();
+}
+
 // One grid pair's constants: the two grid indices (the second repeats the first past an odd
 // grid's end), c1 / c2 / g1a, the pass-1 weight and scan tables, B^1, B^2, B^4, B^8 of the
 // next scan and Bj = B^(lane & 15)
@@ -1554,22 +1619,33 @@ struct GridPair {
   v2f c1, c2, g1a;
   Mat2 Bj, Bp[4];
   __device__ __forceinline__ GridPair(const SmoothArgs& a, int pi, int lane) {
+    // the lane's Bj, requested first: two 16-byte loads whose latency the season's pass 1
+    // covers (the first use is the scan after it)
+    request_bj(a, pi, lane);
     c0 = 2 * pi;
     c1i = (2 * pi + 1 < a.G) ? 2 * pi + 1 : c0;
     const cfp tab = const_ptr(a.pair_tab + (size_t)pi * PairTab<K>::SIZE);
     c1 = ldv2(tab); c2 = ldv2(tab + 2); g1a = ldv2(tab + 4);
     W = tab + PairTab<K>::W0;
     tb = tab + PairTab<K>::B0;
-    const v2f one = splat2(1.f), zero = splat2(0.f);
-    Bj.a = one; Bj.b = zero; Bj.c = zero; Bj.d = one;
 #pragma unroll
     for (int bit = 0; bit < 4; ++bit) Bp[bit] = ldmat(tb + 8 * bit);
-    fence_sched();  // all four requested before the first is used: one scalar-cache wait, not four
-#pragma unroll
-    for (int bit = 0; bit < 4; ++bit) {
-      const Mat2 r = matmul(Bj, Bp[bit]);
-      if ((lane >> bit) & 1) Bj = r;
-    }
+  }
+  __device__ __forceinline__ void request_bj(const SmoothArgs& a, int pi, int lane) {
+    const float4* bj = (const float4*)(lane_powers<K>(a, pi) + 8 * (lane & 15));
+    const float4 b0 = bj[0], b1 = bj[1];
+    Bj.a = {b0.x, b0.y}; Bj.b = {b0.z, b0.w}; Bj.c = {b1.x, b1.y}; Bj.d = {b1.z, b1.w};
+  }
+  // The second pair of a quad (rows 4q .. 4q + 3 share alpha and beta, bit for bit): pair
+  // 2q + 1 differs from pair 2q in the grid indices and g1a only; c1, c2, W, tb and Bp stay.
+  // Its Bj holds the same bits too, but is requested again (the replay covers the two loads):
+  // kept in its eight registers from the first pair's walk into the replay, hw_d_kernel<45>
+  // took 226 registers instead of 218 (docs/PERF.md, "Per-pair set-up").
+  __device__ __forceinline__ void to_sibling(const SmoothArgs& a, int pi, int lane) {
+    request_bj(a, pi, lane);
+    c0 = 2 * pi;
+    c1i = (2 * pi + 1 < a.G) ? 2 * pi + 1 : c0;
+    g1a = ldv2(const_ptr(a.pair_tab + (size_t)pi * PairTab<K>::SIZE) + 4);
   }
 };
 
@@ -1735,9 +1811,8 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
   // copied from scalar to vector registers at the end of every season (16 copies, 32
   // registers), also on the pair queue's path.
   constexpr int ALONE = 0, FIRST = 1, SECOND = 2;
-  const auto walk = [&](auto mode, int pi) __attribute__((always_inline)) {
+  const auto walk = [&](auto mode, GridPair<K>& gp) __attribute__((always_inline)) {
     constexpr int MODE = decltype(mode)::value;
-    GridPair<K> gp(a, pi, lane);
     v2f X1, X2, sse, p1, p2;
     if constexpr (MODE == SECOND) {
       d_replay<K>(mydl, mydl + SEA, gp.W, E, gp.g1a, D, p1, p2);
@@ -1791,11 +1866,14 @@ __device__ __forceinline__ void hw_d_block(const SmoothArgs& a, int hmax, int n0
   };
   for (int k = w; k < n_items;) {
     const int item = quads ? qq.at(k, pi_lo) : hint_pair_at(k, pi_lo, hints_pp);
-    if (item & QUAD_ITEM) {
-      walk(std::integral_constant<int, FIRST>(), item & 0xffff);
-      walk(std::integral_constant<int, SECOND>(), (item & 0xffff) + 1);
+    if (item & QUAD_ITEM) {  // one set-up for the quad: its second pair takes its own g1a
+      GridPair<K> gp(a, item & 0xffff, lane);
+      walk(std::integral_constant<int, FIRST>(), gp);
+      gp.to_sibling(a, (item & 0xffff) + 1, lane);
+      walk(std::integral_constant<int, SECOND>(), gp);
     } else {
-      walk(std::integral_constant<int, ALONE>(), item);
+      GridPair<K> gp(a, item, lane);
+      walk(std::integral_constant<int, ALONE>(), gp);
     }
     k = queue_pop(L.ubound + L.QUEUE, lane, nwaves);
   }
@@ -2551,7 +2629,8 @@ static hipError_t launch_q_fit(const SmoothArgs* a, const float* tab_g, int hmax
 
 // Variant 5 at m = 16 K: hw_q_kernel over quads, then the gapped kernel at K / 2 (32 lanes x
 // K / 2 steps) over the pairs it deferred, with `tab_g` = pair_table(grid, K / 2) (the
-// 32-lane kernel's weights and powers).  Same workspace and contract as fm_hw_d_fit.
+// 32-lane kernel's weights and powers).  Same workspace and contract as fm_hw_d_fit;
+// `a->pair_tab` carries the lane-power section (see fm_hw_d_fit_split_dt), `tab_g` need not.
 // `fp32`: the ring's element type (0: bf16, else fp32).
 extern "C" int fm_hw_q_fit_dt(const SmoothArgs* a, const float* tab_g, int hmax, int* deferred, hipStream_t st,
                               int fp32) {
@@ -2698,7 +2777,10 @@ static hipError_t launch_d_fit(const SmoothArgs* a, int hmax, int* deferred, int
 // on entry (they are left zero).  `grid_quads`: G % 4 == 0 and grid rows 4q .. 4q + 3 carry
 // the same (alpha, beta), bit for bit (the caller checks it once per grid): hw_d_kernel then
 // walks season 1 once per (alpha, beta) (see QuadQueue).  `fp32`: the ring's element type
-// (0: bf16, else fp32).
+// (0: bf16, else fp32).  `a->pair_tab` is the whole table of kernels.pair_table at K: the
+// PairTab rows, the powers of A and the lane-power section filled by fm_hw_lane_powers (the
+// kernel reads it at npairs * (SIZE + 8 (K + 1)) + 128 * pair; a table without it is read
+// out of bounds, and no size is passed that could be checked here).
 extern "C" int fm_hw_d_fit_split_dt(const SmoothArgs* a, int hmax, int* deferred, int* split_ws, int max_split,
                                     int slots, hipStream_t st, int grid_quads, int fp32) {
   const int K = a->K;

@@ -277,20 +277,27 @@ def smoothing_geometry(mode: int, T: int, m: int, K: Optional[int] = None):
 _PAIR_TAB_CACHE: Dict[tuple, torch.Tensor] = {}
 
 
-def pair_table(grid: torch.Tensor, K: int) -> torch.Tensor:
-    """Per combo-pair precomputed table for the table-driven HW kernel
-    (hw_scan.hip ``PairTab``): c1, c2, g1a; pass-1 weights W_i = A^(K-1-i) c;
-    B^1, B^2, B^4, B^8, B^16 with B = A^K — all in (forecast, trend)
-    coordinates, A = [[1-c1, 1], [-c2, 1]], c = (c1, c2), computed in float64."""
-    key = (grid.data_ptr(), tuple(grid.shape), K, grid.device)
-    t = _PAIR_TAB_CACHE.get(key)
-    if t is not None:
-        return t
-    import numpy as np
-    g = grid.detach().cpu().double().numpy()
-    G = g.shape[0]
+LANE_POWERS = 16 * 8   # floats per pair in the pair table's third section: B^0 .. B^15
+
+
+def pair_table_sections(G: int, K: int) -> Tuple[int, int, int, int]:
+    """(row size, offset of the powers of A, offset of the lane powers, total) of
+    :func:`pair_table` for a grid of ``G`` rows at ``K``, in floats: what hw_scan.hip computes
+    from ``PairTab<K>::SIZE``, the pair count and K."""
     npairs = (G + 1) // 2
     size = ((6 + 4 * K + 40) + 15) // 16 * 16
+    pw0 = npairs * size
+    lp0 = pw0 + npairs * (K + 1) * 8
+    return size, pw0, lp0, lp0 + npairs * LANE_POWERS
+
+
+def pair_table_host(g, K: int):
+    """The host-built sections of :func:`pair_table` for the grid rows ``g`` (float64 numpy,
+    [G, 3]) as one float32 array; the lane-power section at its end is left zero."""
+    import numpy as np
+    G = g.shape[0]
+    npairs = (G + 1) // 2
+    size = pair_table_sections(G, K)[0]
     tab = np.zeros((npairs, size), dtype=np.float64)
     for p in range(npairs):
         for comp, ci in enumerate((2 * p, 2 * p + 1 if 2 * p + 1 < G else 2 * p)):
@@ -333,8 +340,29 @@ def pair_table(grid: torch.Tensor, K: int) -> torch.Tensor:
                 for q, v in enumerate((Ap[0, 0], Ap[0, 1], Ap[1, 0], Ap[1, 1])):
                     pw[p, n, 2 * q + comp] = v
                 Ap = A @ Ap
-    t = torch.tensor(np.concatenate([tab.reshape(-1), pw.reshape(-1)]), dtype=torch.float32,
-                     device=grid.device).contiguous()
+    return np.concatenate([tab.reshape(-1), pw.reshape(-1), np.zeros(npairs * LANE_POWERS)]).astype(np.float32)
+
+
+def pair_table(grid: torch.Tensor, K: int) -> torch.Tensor:
+    """Per combo-pair precomputed table for the table-driven HW kernel
+    (hw_scan.hip ``PairTab``): c1, c2, g1a; pass-1 weights W_i = A^(K-1-i) c;
+    B^1, B^2, B^4, B^8, B^16 with B = A^K — all in (forecast, trend)
+    coordinates, A = [[1-c1, 1], [-c2, 1]], c = (c1, c2), computed in float64.
+    Then A^0 .. A^K per pair (the gapped kernel's), then B^0 .. B^15 per pair
+    ([npairs][16][8]: a lane's Bj of the variant-5 scans), which the device fills once, here,
+    from the table's own fp32 B^1 .. B^8 (``fm_hw_lane_powers``)."""
+    key = (grid.data_ptr(), tuple(grid.shape), K, grid.device)
+    t = _PAIR_TAB_CACHE.get(key)
+    if t is not None:
+        return t
+    g = grid.detach().cpu().double().numpy()
+    t = torch.from_numpy(pair_table_host(g, K)).to(grid.device).contiguous()
+    if t.is_cuda:
+        rc = nat.require().fm_hw_lane_powers(nat.ptr(t), (g.shape[0] + 1) // 2, int(K), nat.stream_handle(t.device))
+        nat.check(rc, "fm_hw_lane_powers")
+        # once per table: whichever stream fits from it.  Like the fit launchers, this relies on
+        # the caller's current device being the grid's
+        torch.cuda.current_stream(t.device).synchronize()
     if len(_PAIR_TAB_CACHE) > 64:
         _PAIR_TAB_CACHE.clear()
     _PAIR_TAB_CACHE[key] = t
