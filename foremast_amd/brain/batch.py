@@ -29,6 +29,7 @@ from ..models import bivariate as biv_ref
 from ..models import multivariate_normal as mvn_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
+from ..models import robust_average as rb_ref
 from ..models import pairwise as pw_ref
 from ..models import prophet_lite as pl_ref
 from ..models import smoothing as sm_ref
@@ -205,9 +206,10 @@ class BatchScorer:
             else:
                 h = t_hist
                 head, length = 0, T
-                if algo == "moving_average" and cfg.ma_window < T:
+                if algo in ("moving_average", "robust_average") and cfg.ma_window < T:
                     head, length = T - cfg.ma_window, cfg.ma_window
-                out = K.window_stats(h, head, length, spec)
+                stats = K.robust_stats if algo in ("robust_average", "robust_average_all") else K.window_stats
+                out = stats(h, head, length, spec)
             upper, lower = out["upper"], out["lower"]
             verdict = out["verdict"]
             anom = None
@@ -226,6 +228,11 @@ class BatchScorer:
                 sigma1 = sigma
                 if cfg.horizon_variance:
                     sigma = sigma[:, None] * det_ref.horizon_sigma_factor(grid[fit.best.long()], mode, max(m, 1), t_hz)
+            elif algo in ("robust_average", "robust_average_all"):
+                rs = rb_ref.robust_stats(t_hist, cfg.ma_window if algo == "robust_average" else None)
+                f = rs.center[:, None].expand(B, t_cur.shape[1])
+                sigma, n_valid = rs.sigma, rs.count
+                sigma1 = sigma
             else:
                 st = ma_ref.window_stats(t_hist, cfg.ma_window if algo == "moving_average" else None)
                 f = st.mean[:, None].expand(B, t_cur.shape[1])

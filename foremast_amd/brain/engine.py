@@ -30,6 +30,7 @@ from ..models import bivariate as biv_ref
 from ..models import multivariate_normal as mvn_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
+from ..models import robust_average as rb_ref
 from ..models import pairwise as pw_ref
 from ..models import smoothing as sm_ref
 from ..utils.config import BrainConfig
@@ -693,13 +694,14 @@ class StreamingShard:
                 K.hw_detect_deferred(self.out, spec, Tp, self.spec.season, grid=self.grid)
             if self.refit_every > 1 and head_dev is None:
                 self._refresh_cache_gpu()
-        elif self.algorithm in ("moving_average_all", "moving_average"):
+        elif self.algorithm in ("moving_average_all", "moving_average", "robust_average_all", "robust_average"):
             length = h.length
             head = h.head
-            if self.algorithm == "moving_average" and cfg.ma_window < length:
+            if self.algorithm in ("moving_average", "robust_average") and cfg.ma_window < length:
                 head = (h.head + length - cfg.ma_window) % h.R
                 length = cfg.ma_window
-            self.out = K.window_stats(h.data, head, length, spec, out=self.out)
+            stats = K.robust_stats if self.algorithm.startswith("robust") else K.window_stats
+            self.out = stats(h.data, head, length, spec, out=self.out)
         elif self.algorithm == "seasonal_decompose":
             self.out = K.decompose_score(h.data, h.head, h.length, self.spec.season, spec, out=self.out)
         elif self.algorithm == "prophet":
@@ -763,6 +765,12 @@ class StreamingShard:
                 self._new_pts = 0
             else:
                 self._cache = None
+        elif self.algorithm in ("robust_average_all", "robust_average"):
+            rs = rb_ref.robust_stats(y, cfg.ma_window if self.algorithm == "robust_average" else None)
+            f = rs.center[:, None].expand(-1, h.shape[0])
+            sigma = rs.sigma
+            n_valid = rs.count
+            extra = {"center": rs.center, "sigma": rs.sigma, "mad": rs.mad}
         else:
             win = cfg.ma_window if self.algorithm == "moving_average" else None
             st = ma_ref.window_stats(y, win)

@@ -43,7 +43,7 @@ from ..utils.timeutil import TimeFormatError, parse_rfc3339
 
 STRATEGIES = ("canary", "rollingupdate")
 UNIVARIATE = ("holt_winters", "exponential_smoothing", "double_exponential_smoothing", "moving_average",
-              "moving_average_all", "seasonal_decompose", "prophet")
+              "moving_average_all", "seasonal_decompose", "prophet", "robust_average", "robust_average_all")
 # multi-metric algorithms (docs/guides/design.md:53-89): every metric keeps a univariate
 # row (moving_average_all, as brain/batch.py scores it), and the job gets a joint model
 JOINT_ALGORITHMS = ("bivariate_normal", "multivariate_normal", "lstm", "auto")

@@ -82,6 +82,7 @@ from ..models import bivariate as biv_ref
 from ..models import decompose as dec_ref
 from ..models import detect as det_ref
 from ..models import moving_average as ma_ref
+from ..models import robust_average as rb_ref
 from ..models import multivariate_normal as mvn_ref
 from ..models import pairwise as pw_ref
 from ..models import prophet_lite as pr_ref
@@ -1011,8 +1012,13 @@ class RolloutMonitor:
                         "season_hb": out["forecast"] - out["level"][:, None] - hs[None, :] * out["slope"][:, None],
                         "best": torch.full((k,), -1, dtype=torch.int32, device=dev)}
             h0, ln = head, length
-            if algo == "moving_average" and cfg.ma_window < length:
+            if algo in ("moving_average", "robust_average") and cfg.ma_window < length:
                 h0, ln = (head + length - cfg.ma_window) % data.shape[1], cfg.ma_window
+            if algo in ("robust_average", "robust_average_all"):
+                out = K.robust_stats(data, h0, ln, spec)
+                return {"level": out["center"], "trend": torch.zeros(k, device=dev), "sigma": out["sigma"],
+                        "nvalid": out["count_hist"], "season_hb": torch.zeros((k, HB), device=dev),
+                        "best": torch.full((k,), -1, dtype=torch.int32, device=dev)}
             out = K.window_stats(data, h0, ln, spec)
             return {"level": out["mean"], "trend": torch.zeros(k, device=dev), "sigma": out["std"],
                     "nvalid": out["count_hist"], "season_hb": torch.zeros((k, HB), device=dev),
@@ -1034,6 +1040,10 @@ class RolloutMonitor:
             return {"level": fc.level, "trend": fc.slope, "sigma": fc.sigma, "nvalid": fc.n_valid.float(),
                     "season_hb": f - fc.level[:, None] - hsl[None, :] * fc.slope[:, None],
                     "best": torch.full((k,), -1, dtype=torch.int32)}
+        if algo in ("robust_average", "robust_average_all"):
+            rs = rb_ref.robust_stats(y, cfg.ma_window if algo == "robust_average" else None)
+            return {"level": rs.center, "trend": torch.zeros(k), "sigma": rs.sigma, "nvalid": rs.count.float(),
+                    "season_hb": torch.zeros((k, HB)), "best": torch.full((k,), -1, dtype=torch.int32)}
         ws = ma_ref.window_stats(y, cfg.ma_window if algo == "moving_average" else None)
         return {"level": ws.mean, "trend": torch.zeros(k), "sigma": ws.std, "nvalid": ws.count.float(),
                 "season_hb": torch.zeros((k, HB)), "best": torch.full((k,), -1, dtype=torch.int32)}

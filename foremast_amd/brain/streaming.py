@@ -220,7 +220,7 @@ class StreamingMonitor:
         algo = self.cfg.algorithm if self.cfg.algorithm in ("holt_winters", "exponential_smoothing",
                                                             "double_exponential_smoothing", "moving_average",
                                                             "moving_average_all", "seasonal_decompose",
-                                                            "prophet") \
+                                                            "prophet", "robust_average", "robust_average_all") \
             else "moving_average_all"
         if algo == "holt_winters" and self.R < 2 * season:
             algo = "double_exponential_smoothing"

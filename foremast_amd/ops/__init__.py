@@ -6,6 +6,7 @@ Kernels (``csrc/``), each with a PyTorch reference in ``foremast_amd.models``:
 K#          kernel                        reference
 ==========  ============================  ==========================================
 K1          ``window_stats``              models/moving_average.py
+K1 (robust) ``robust_stats``              models/robust_average.py
 K2/K3       ``smooth_fit`` (ES/DES/HW)    models/smoothing.py
 K5/K11      ``rank_tests``                models/pairwise.py
 K6/K7       ``lstm_*``                    models/lstm_ae.py

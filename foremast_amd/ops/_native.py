@@ -73,6 +73,13 @@ class WindowArgs(C.Structure):
     ]
 
 
+class RobustArgs(C.Structure):
+    _fields_ = [
+        ("hist", P), ("ld", LL), ("ring_len", I), ("head", I), ("len", I), ("N", I),
+        ("center", P), ("stdv", P), ("count", P), ("det", DetectArgs), ("mad", P), ("sigma", P),
+    ]
+
+
 class BivArgs(C.Structure):
     _fields_ = [
         ("hx", P), ("hy", P), ("ld", LL), ("ring_len", I), ("head", I), ("len", I), ("N", I),
@@ -178,6 +185,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.fm_rank_lds_bytes.restype = C.c_size_t
     lib.fm_window_stats.argtypes = [C.POINTER(WindowArgs), I, P]
     lib.fm_window_stats.restype = I
+    lib.fm_robust_stats.argtypes = [C.POINTER(RobustArgs), I, P]
+    lib.fm_robust_stats.restype = I
     lib.fm_bivariate.argtypes = [C.POINTER(BivArgs), I, P]
     lib.fm_bivariate.restype = I
     lib.fm_bivariate_pairs.argtypes = [C.POINTER(BivPairArgs), I, P]

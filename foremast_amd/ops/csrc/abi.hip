@@ -9,6 +9,7 @@ extern "C" long long fm_abi_sizeof(const char* name) {
   if (!__builtin_strcmp(name, "SmoothArgs")) return sizeof(SmoothArgs);
   if (!__builtin_strcmp(name, "RankArgs")) return sizeof(RankArgs);
   if (!__builtin_strcmp(name, "WindowArgs")) return sizeof(WindowArgs);
+  if (!__builtin_strcmp(name, "RobustArgs")) return sizeof(RobustArgs);
   if (!__builtin_strcmp(name, "BivArgs")) return sizeof(BivArgs);
   if (!__builtin_strcmp(name, "BivPairArgs")) return sizeof(BivPairArgs);
   if (!__builtin_strcmp(name, "MvnGroupArgs")) return sizeof(MvnGroupArgs);
@@ -25,6 +26,7 @@ extern "C" long long fm_abi_offsetof(const char* name, const char* field) {
     FM_OFF(DetectArgs, row_out); FM_OFF(DetectArgs, tick_min); FM_OFF(DetectArgs, shift_one_step); }
   if (!__builtin_strcmp(name, "RankArgs")) { FM_OFF(RankArgs, pvals); FM_OFF(RankArgs, alpha); FM_OFF(RankArgs, p_friedman); FM_OFF(RankArgs, pods_b); FM_OFF(RankArgs, z_crit); }
   if (!__builtin_strcmp(name, "WindowArgs")) { FM_OFF(WindowArgs, det); }
+  if (!__builtin_strcmp(name, "RobustArgs")) { FM_OFF(RobustArgs, det); FM_OFF(RobustArgs, mad); FM_OFF(RobustArgs, sigma); }
   if (!__builtin_strcmp(name, "BivArgs")) { FM_OFF(BivArgs, eps); FM_OFF(BivArgs, app_stats); }
   if (!__builtin_strcmp(name, "BivPairArgs")) { FM_OFF(BivPairArgs, threshold); FM_OFF(BivPairArgs, anom_val); }
   if (!__builtin_strcmp(name, "MvnGroupArgs")) { FM_OFF(MvnGroupArgs, thr2); FM_OFF(MvnGroupArgs, contrib); FM_OFF(MvnGroupArgs, anom_val); FM_OFF(MvnGroupArgs, kmask); }

@@ -131,6 +131,23 @@ struct WindowArgs {
   DetectArgs det;
 };
 
+// robust_average / robust_average_all (robust.hip): WindowArgs' ring contract, with the
+// lower median, its MAD and the sigma the band uses next to the window's std.
+struct RobustArgs {
+  const void* hist;
+  long long ld;
+  int ring_len;
+  int head;      // physical column of the first sample of the window
+  int len;       // window length (logical samples)
+  int N;
+  float* center; // [N] lower median (NaN: no valid sample)
+  float* stdv;   // [N] population standard deviation
+  float* count;  // [N]
+  DetectArgs det;
+  float* mad;    // [N] lower median of |y - center|
+  float* sigma;  // [N] 1.4826 mad, or stdv where mad == 0
+};
+
 struct BivArgs {
   const void* hx;       // [N, ld] metric 0 ring
   const void* hy;       // [N, ld] metric 1 ring

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "detect.h"
 #include "args.h"
+#include "winsum.h"
 
 // ---------------------------------------------------------------------------------
 // ring append: dst[n, (col0 + j) % R] = src[n, j]   (j < S)
@@ -56,48 +57,6 @@ extern "C" int fm_ring_append(void* dst, long long ld_dst, int R, int col0, int 
 
 
 
-// Accumulate shifted sums over physical range [p0, p1) of a row; vector body
-// of 16-byte loads, scalar head/tail.
-template <typename TIN, int UNR = 6>
-__device__ __forceinline__ void acc_range(const TIN* row, int p0, int p1, float& shift, bool& has_shift,
-                                          float& n, float& s1, float& s2, int tid, int nt) {
-  constexpr int VEC = 16 / sizeof(TIN);
-  auto add = [&](float v) {
-    if (v == v) {
-      if (!has_shift) { shift = v; has_shift = true; }
-      const float d = v - shift;
-      n += 1.f; s1 += d; s2 += d * d;
-    }
-  };
-  int a0 = p0 + ((VEC - (p0 % VEC)) % VEC);
-  if (a0 > p1) a0 = p1;
-  for (int i = p0 + tid; i < a0; i += nt) add(to_f32<TIN>(row[i]));
-  const int nvec = (p1 - a0) / VEC;
-  // UNR 16-byte loads of a thread in flight at once (clamped index, no branch before the
-  // loads), then the accumulation: one memory latency per UNR vectors instead of one each
-  for (int v0 = tid; v0 < nvec; v0 += nt * UNR) {
-    uint4 q[UNR];
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) q[u] = *(const uint4*)(row + a0 + min(v0 + u * nt, nvec - 1) * VEC);
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      if (v0 + u * nt >= nvec) break;
-      if (sizeof(TIN) == 2) {
-        const unsigned w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          add(__uint_as_float(w[k] << 16));
-          add(__uint_as_float(w[k] & 0xffff0000u));
-        }
-      } else {
-        add(__uint_as_float(q[u].x)); add(__uint_as_float(q[u].y));
-        add(__uint_as_float(q[u].z)); add(__uint_as_float(q[u].w));
-      }
-    }
-  }
-  for (int i = a0 + nvec * VEC + tid; i < p1; i += nt) add(to_f32<TIN>(row[i]));
-}
-
 // One wave per series (kSeriesPerWG per workgroup): the same statistics with wave
 // reductions only, no workgroup barriers, and ~20 16-byte loads of a lane in flight in
 // two batches.
@@ -119,15 +78,9 @@ __global__ __launch_bounds__(kWindowBlock) void window_stats_wave_kernel(const W
     acc_range<TIN, 10>(row, p0, a.ring_len, shift, has, cnt, s1, s2, lane, FM_WAVE);
     acc_range<TIN, 10>(row, 0, p1 - a.ring_len, shift, has, cnt, s1, s2, lane, FM_WAVE);
   }
-  // per-lane (n, mean, M2) -> Chan merge about the count-weighted mean of the lane means
-  const float mean_t = cnt > 0.f ? shift + s1 / cnt : 0.f;
-  const float m2_t = cnt > 0.f ? fmaxf(s2 - s1 * s1 / cnt, 0.f) : 0.f;
-  const float N = wave_sum(cnt);
-  const float sm = wave_sum(cnt * mean_t);
-  const float ref = N > 0.f ? sm / N : 0.f;
-  const float dm = mean_t - ref;
-  const float M2 = wave_sum(m2_t + cnt * dm * dm);
-  const float mean = ref;
+  const WaveMoments w = chan_merge_wave(shift, cnt, s1, s2);
+  const float N = w.N, M2 = w.M2;
+  const float mean = w.mean;
   const float var = N > 0.f ? M2 / N : 0.f;
   const float sd = N > 0.f ? sqrtf(fmaxf(var, 0.f)) : fm_nan();
   if (lane == 0) {

@@ -762,6 +762,38 @@ def window_stats(hist: torch.Tensor, head: int, length: int, det: DetectSpec,
     return out
 
 
+def robust_stats(hist: torch.Tensor, head: int, length: int, det: DetectSpec,
+                 out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """Lower median, MAD, std and the band's sigma of a ring window with the fused detection
+    epilogue (csrc/robust.hip; semantics: models/robust_average.py)."""
+    lib = nat.require()
+    _hist_check(hist, head, length)
+    dev = hist.device
+    N = hist.shape[0]
+    bf16 = hist.dtype == torch.bfloat16
+    _need(hist.stride(0) % (8 if bf16 else 4) == 0 and hist.data_ptr() % 16 == 0,
+          "hist rows must be 16-byte aligned for vector loads")
+    out = {} if out is None else out
+    for k in ("center", "sigma", "mad", "std", "count_hist"):
+        if k not in out:
+            out[k] = torch.empty(N, dtype=torch.float32, device=dev)
+    a = nat.RobustArgs()
+    a.hist = nat.ptr(hist)
+    a.ld = hist.stride(0)
+    a.ring_len = hist.shape[1]
+    a.head = int(head)
+    a.len = int(length)
+    a.N = N
+    a.center = nat.ptr(out["center"])
+    a.stdv = nat.ptr(out["std"])
+    a.count = nat.ptr(out["count_hist"])
+    a.mad = nat.ptr(out["mad"])
+    a.sigma = nat.ptr(out["sigma"])
+    _fill_detect(a.det, det, N, dev, out)
+    nat.check(lib.fm_robust_stats(a, int(bf16), nat.stream_handle(dev)), "fm_robust_stats")
+    return out
+
+
 _ZC: Dict[float, float] = {}
 
 

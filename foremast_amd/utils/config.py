@@ -30,7 +30,7 @@ BOUND_LOWER = 2
 BOUND_BOTH = 3
 
 ALGORITHMS = (
-    "moving_average", "moving_average_all", "exponential_smoothing",
+    "moving_average", "moving_average_all", "robust_average", "robust_average_all", "exponential_smoothing",
     "double_exponential_smoothing", "holt_winters", "prophet", "seasonal_decompose",
     "bivariate_normal", "multivariate_normal", "lstm",
 )
